@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — stereo pairs/s of the HIP training step @320x240 bf16 on 1..8 MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, the analytic
+`step_roofline`). `--full` adds every other measurement described below, each of which takes GPU or host runs of its
+own: `clock`, `roofline` / `gemm_kernels` / `encoder_conv_roofline`, `epe`, `infer_960x720`, `cpu_baseline` and
+`comm`'s exposed all-reduce time (the --no-* switches and --epe-steps select among them). `--dump-outputs DIR` writes
+what the last timed step left its caller (dump_outputs below) as DIR/<name>.npy.
 
 A "step" = one full training step of StereoUNet(base 32) on one batch of 64 synthetic
 320x240 stereo pairs per GPU (BASELINE.json configs[1]; configs[2] at N=8): pack weights,
@@ -56,6 +62,11 @@ def parse():
     ap.add_argument("--height", type=int, default=240)
     ap.add_argument("--width", type=int, default=320)
     ap.add_argument("--precision", default="bf16", choices=("bf16", "fp32"))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left its caller as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure: clock probe, per-kernel roofline "
+                         "region, EPE training, 960x720 inference, CPU baseline (the switches below select among them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-roofline", action="store_true")
@@ -285,6 +296,36 @@ def lib_sha256() -> str:
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "stereo_depth_estimation_amd", "libstereo_hip.so")
     with open(path, "rb") as f:
         return hashlib.sha256(f.read()).hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(torch, model, path: str):
+    """--dump-outputs: what train_step has left its caller after the last timed step, as DIR/<name>.npy.
+
+    A train step returns nothing; its results are the state it updates in place. `params` and `grads` are the model's
+    flat fp32 buffers (StereoUNet.flat_buffers(): every trainable tensor in backward-production order, the updated
+    weights and the gradients of the last step), `bn_running_mean` / `bn_running_var` the BatchNorm running statistics
+    concatenated in module order, `metrics` the engine's float64 sums (nll, |d|, d^2, sigma, n) over all steps run.
+    Model init, batches and step count depend on the arguments only, so two builds can be compared array for array."""
+    import numpy as np
+
+    torch.cuda.synchronize()
+    flat_p, flat_g = model.flat_buffers()
+    bns = [m for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+    out = {"params": flat_p, "grads": flat_g, "metrics": model._engine.metrics,
+           "bn_running_mean": torch.cat([m.running_mean.reshape(-1) for m in bns]),
+           "bn_running_var": torch.cat([m.running_var.reshape(-1) for m in bns])}
+    arrays = {k: v.detach().cpu().numpy() for k, v in out.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(path, k + ".npy"), a)
+    log(f"--dump-outputs: {len(arrays)} arrays, {total / 1e6:.1f} MB in {path}")
 
 
 def pmc_traffic(kernel: str):
@@ -597,7 +638,7 @@ def main():
     torch.cuda.synchronize()
     log(f"warmup {args.warmup} steps: {time.perf_counter() - t_w:.1f}s")
 
-    clk_before = clock_probe(torch, L, dev)
+    clk_before = clock_probe(torch, L, dev) if args.full else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -608,13 +649,15 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
-    clk_after = clock_probe(torch, L, dev)
+    clk_after = clock_probe(torch, L, dev) if args.full else None
+    if args.dump_outputs and rank == 0:  # before anything below steps the model again
+        dump_outputs(torch, model, args.dump_outputs)
 
     # Per-kernel HIP-event timing runs over a second K-step region right after the timed one: an
     # event record between two launches is a barrier packet on the stream (it serialises the queue
     # and added ~0.5 ms per step, 4 %), so the headline region carries none.
     timer = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         timer = GemmTimer(torch, L, model._engine)
         L.set_call_hook(timer)
         if ddp is not None:
@@ -654,9 +697,10 @@ def main():
             "batchnorm": "sync" if (args.sync_bn and world > 1) else "per-rank",
         },
     }
-    result["clock"] = {"before": clk_before, "after": clk_after,
-                       "probe": "sd_clock_probe: 256 blocks x 4 waves of back-to-back bf16 MFMAs, ~1 ms, outside the "
-                                "timed region; MHz = d(s_memtime)/d(s_memrealtime) x 100"}
+    if args.full:
+        result["clock"] = {"before": clk_before, "after": clk_after,
+                           "probe": "sd_clock_probe: 256 blocks x 4 waves of back-to-back bf16 MFMAs, ~1 ms, outside "
+                                    "the timed region; MHz = d(s_memtime)/d(s_memrealtime) x 100"}
     if share:
         result["rehearsal"] = f"gloo, {world} ranks sharing cuda:0 (SD_BENCH_SHARE_DEVICE=1): not a scaling number"
     if world > 1:
@@ -712,13 +756,13 @@ def main():
         result["clock"]["dominant_kernel"] = {"kernel": top["kernel"], "avg_launch_us": round(top["avg_us"], 2)}
         result["gemm_kernels"] = [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()} for r in kern]
         result["encoder_conv_roofline"] = timer.encoder_roofline(args.steps, peak)
-    if world == 1 and args.epe_steps > 0:
+    if args.full and world == 1 and args.epe_steps > 0:
         log(f"EPE: {args.epe_steps} synthetic training steps, then bf16 / fp32 / oracle validation ...")
         result["epe"] = epe_block(torch, model, opt, dev, args.epe_steps)
-    if rank == 0 and world == 1 and not args.no_infer:
+    if args.full and rank == 0 and world == 1 and not args.no_infer:
         log("fp8 inference (config 5) ...")
         result["infer_960x720"] = infer_fp8(torch, model, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline ...")
         result["cpu_baseline"] = cpu_baseline(args.cpu_seconds, H, W)
         held = getattr(epe_block, "held", None)

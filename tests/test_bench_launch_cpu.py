@@ -60,6 +60,15 @@ def test_bench_world_size_mismatch_exits_nonzero():
     assert not r.stdout.strip()
 
 
+def test_full_is_off_by_default_and_dump_outputs_takes_a_directory(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "some/dir", "--no-infer"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "some/dir" and a.no_infer
+
+
 def test_step_roofline_prices_surveys_85_gflop_step():
     """the whole-step conv roofline. Its GEMM table must carry the survey's
     85.025 GFLOP per training pair at 320x240 (fwd 28.430 + dgrad 28.165 + wgrad 28.430), and the attainable time at

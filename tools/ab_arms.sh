@@ -8,7 +8,7 @@ for r in $(seq 1 $R); do
   for SET in "$@"; do
     i=$((i + 1))
     [ "$SET" = "-" ] && SET="SD_NONE=1"
-    env $SET SD_BENCH_LAYERS=1 timeout -k 10 200 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-infer \
+    env $SET SD_BENCH_LAYERS=1 timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-infer \
         > "$OUT/b_${i}_$r.json" 2> "$OUT/b_${i}_$r.err" || exit 3
     echo "arm $i ($SET) round $r: $(grep -o '"value": [0-9.]*' "$OUT/b_${i}_$r.json" | head -1)"
   done

@@ -6,7 +6,7 @@ OUT=$(pwd)/gpurun_out/$TAG
 mkdir -p "$OUT"
 for v in intree "$@"; do
     if [ "$v" = intree ]; then unset SD_HIP_LIB; else export SD_HIP_LIB=$(pwd)/build_ab/$v; fi
-    SD_BENCH_LAYERS=1 timeout -k 10 200 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-infer \
+    SD_BENCH_LAYERS=1 timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-infer \
         > "$OUT/b_$v.json" 2> "$OUT/b_$v.err" || exit 3
     grep -o '"value": [0-9.]*' "$OUT/b_$v.json" | head -1
 done

@@ -8,11 +8,11 @@ TAG=${1:-prof}
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
-timeout -k 10 300 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
 tail -c 400 "$OUT/bench.json"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-    python3 "$ROOT/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-infer --epe-steps 0 > "$OUT/prof.log" 2>&1 || exit $?
+    python3 "$ROOT/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-infer --epe-steps 0 > "$OUT/prof.log" 2>&1 || exit $?
 cd "$ROOT"
 bash tools/pmc_round.sh "${TAG}_tr" || exit $?
 bash tools/pmc_sq.sh "${TAG}_sq" || exit $?
