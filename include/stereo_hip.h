@@ -397,6 +397,60 @@ int sd_stereo_from_cache(const uint8_t* left, const uint8_t* right, const uint16
 int sd_augment_rgb(float* input, int batch, int H, int W, const float* params, int blur_ksize, uint64_t seed,
                    float* work, sd_stream s);
 
+/* ---- on-device frame path of the live loop (live_camera/depth_live_dl.py around model(x)) ----
+ * Frames are BGR uint8 [Hc][Wc][3] as cv2 captures them; the model runs at [H][W]; B = 1. All buffers are the
+ * caller's, nothing allocates or synchronises (graph-capturable).
+ *
+ * Front end (depth_live_dl.py:476-493 cv2.remap, :225-229 cvtColor / resize / /255, :516-520 cat + upload) and the
+ * engine's input pack in one pass. Per side, optional rectification maps in OpenCV's CV_16SC2 fixed-point format (as
+ * RectificationData holds them): map1 int16 [Hc][Wc][2] = integer x, y; map2 uint16 [Hc][Wc], low 10 bits =
+ * fy5 << 5 | fx5, fractions in 1/32 px (NULL, NULL: no rectification). Remap: bilinear, a tap outside the frame
+ * contributes 0. Resize: bilinear on half-pixel centres with edge replicate, taken over the remapped image (<= 16 source
+ * taps per value). fp32 throughout, / 255 last. OpenCV's uint8 intermediate and fixed-point tables are not reproduced.
+ *   xin  : NHWC dtype (SD_F32 / SD_BF16), 8 channels [L_R, L_G, L_B, R_R, R_G, R_B, 0, 0]: the engine's input,
+ *          bit-identical to sd_pack_input(dtype, nchw, 1, 6, H, W, 8, xin)
+ *   nchw : optional f32 [6][H][W], the reference's model_input
+ *   amax : optional; as sd_pack_input_amax (atomicMax of max|x| into amax[slot], amax[clear] zeroed, clear < 0: none) */
+int sd_live_frontend(int dtype, const uint8_t* left, const uint8_t* right, int Hc, int Wc, const int16_t* map1_l,
+                     const uint16_t* map2_l, const int16_t* map1_r, const uint16_t* map2_r, int H, int W, void* xin,
+                     float* nchw, unsigned* amax, int slot, int clear, sd_stream s);
+/* The rectified view for display (:489): the remap alone, rounded half to even -> uint8 BGR [Hc][Wc][3]. */
+int sd_live_rectify(const uint8_t* frame, int Hc, int Wc, const int16_t* map1, const uint16_t* map2, uint8_t* view,
+                    sd_stream s);
+/* Post stage on the heads' f32 [H][W] maps, numpy float32 arithmetic (scalars are the caller's float32 casts):
+ *   EMA (:531-540)       state = copy ? disp : alpha * disp + one_minus_alpha * state   (copy: first frame or alpha 0)
+ *   depth (:371-377)     depth = focal_baseline / state where state is finite and > 1e-6, else NaN   (depth_on)
+ *   confidence (:380-381) conf = exp(-0.5 * logvar)                                                   (logvar != NULL)
+ *   codes (:237-250, fixed range) code = trunc(clip((v - lo) / scale, 0, 1) * 255) for finite v > 0, else 0; u8 [H][W],
+ *                        depth_code of depth, conf_code of conf (each optional) */
+int sd_live_post(const float* disp, const float* logvar, int H, int W, float* state, int copy, float alpha,
+                 float one_minus_alpha, int depth_on, float focal_baseline, float* depth, float* conf,
+                 uint8_t* depth_code, float depth_lo, float depth_scale, uint8_t* conf_code, float conf_lo,
+                 float conf_scale, sd_stream s);
+/* depth_contour_mask (:254-275): edge u8 [H][W] = 255 where the pixel and its right or lower neighbour are both valid
+ * (finite, > min_depth, <= max_depth) and floor((clip(depth) - min_depth) / step) differs, else 0. */
+int sd_live_contours(const float* depth, int H, int W, float min_depth, float max_depth, float step, uint8_t* edge,
+                     sd_stream s);
+/* The auto range of colorize_scalar_map (:242-244, np.percentile(values, 2 / 98)), exact, on the device: a radix
+ * select over the finite, > 0 values. sel (7 words): [0] the count n as uint32; [1..4] the order statistics at
+ * floor((n-1)*0.02), the next index, floor((n-1)*0.98), the next index (clamped to n-1); [5] lo, [6] hi = float32 of the
+ * fp64 linear interpolation. n == 0: NaN. code (optional, u8 [H][W]): the codes of `values` in that range, all 0 when
+ * n == 0. work: sd_live_select_ws_bytes() bytes, zero before the first call; every call leaves it zero. */
+long long sd_live_select_ws_bytes(void);
+int sd_live_select(const float* values, int H, int W, unsigned* work, float* sel, uint8_t* code, sd_stream s);
+/* The centre read-out (:542-595): out3 = medians of the finite, > 0 values of the centre window (half = max(1,
+ * window / 2) around (H/2, W/2), clipped) of disp, depth, conf (NULL map or empty window: NaN; even count: the float32
+ * mean of the two middle values). window <= 63. */
+int sd_live_center(const float* disp, const float* depth, const float* conf, int H, int W, int window, float* out3,
+                   sd_stream s);
+/* Display images at the view size (:568-574 contour overlay, :601-617 applyColorMap + cv2.resize INTER_LINEAR): vis_x
+ * u8 BGR [Hc][Wc][3] = bilinear resize (half-pixel centres, edge replicate, round half to even) of lut_x[code_x], lut
+ * u8 [256][3] BGR, code u8 [H][W]; left_view = view with (0, 255, 0) where the nearest-resized edge mask
+ * (sx = min(dx * W / Wc, W - 1)) is set. Each of image a, image b and the left view is optional (NULL). */
+int sd_live_compose(const uint8_t* code_a, const uint8_t* lut_a, uint8_t* vis_a, const uint8_t* code_b,
+                    const uint8_t* lut_b, uint8_t* vis_b, const uint8_t* edge, const uint8_t* view, uint8_t* left_view,
+                    int H, int W, int Hc, int Wc, sd_stream s);
+
 #ifdef __cplusplus
 }
 #endif

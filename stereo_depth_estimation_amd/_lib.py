@@ -180,6 +180,14 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_stereo_preprocess": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "sd_stereo_from_cache": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "sd_augment_rgb": (_i, [_p, _i, _i, _i, _p, _i, ctypes.c_uint64, _p, _p]),
+    "sd_live_frontend": (_i, [_i, _p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _i, _i, _p]),
+    "sd_live_rectify": (_i, [_p, _i, _i, _p, _p, _p, _p]),
+    "sd_live_post": (_i, [_p, _p, _i, _i, _p, _i, _f, _f, _i, _f, _p, _p, _p, _f, _f, _p, _f, _f, _p]),
+    "sd_live_contours": (_i, [_p, _i, _i, _f, _f, _f, _p, _p]),
+    "sd_live_select_ws_bytes": (ctypes.c_longlong, []),
+    "sd_live_select": (_i, [_p, _i, _i, _p, _p, _p, _p]),
+    "sd_live_center": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
+    "sd_live_compose": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

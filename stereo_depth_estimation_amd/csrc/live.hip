@@ -1,0 +1,625 @@
+// On-device frame path of the live depth loop (the reference's live_camera/depth_live_dl.py around model(x)):
+// raw uint8 BGR camera frames in, display-ready uint8 images and three scalars out.
+//   front end : cv2.remap + cvtColor + cv2.resize + /255 + cat + upload + the engine's input pack (:476-493,225-229,516-520)
+//   post      : EMA, disparity_to_depth, confidence_from_logvar, colour codes, depth_contour_mask (:531-540,371-381,254-275,232-251)
+//   select    : np.percentile(values, 2 / 98) of the auto range (:242-244), exact, without a host round trip
+//   centre    : the centre-window medians (:542-595)
+//   compose   : applyColorMap + cv2.resize back to the view + the contour overlay (:568-574,601-617)
+// Byte and fp32 streaming kernels, grid-stride (as data.hip): one pixel per thread in the gathering kernels (the front
+// end stores a 16/32-B NHWC vector), four elements per thread with 16-B float and 4-B byte accesses in the plane kernels
+// when counts and pointers allow, else one. No allocation, no synchronisation.
+//
+// Arithmetic: fp32 from the bytes on, every rounding explicit (fmaf, or mul_rn / add_rn / ... under fp contract(off)),
+// so that no contraction choice of the compiler can differ between instantiations: the packed input is bit-identical
+// to sd_pack_input of the NCHW output, and the post stage reproduces numpy's float32 arithmetic (Python-float scalars
+// cast to float32 first, NEP 50).
+// OpenCV's intermediate uint8 rounding and its fixed-point coefficient tables are NOT reproduced.
+#include <limits.h>
+#include <math.h>
+
+#include "common.h"
+
+// No contraction anywhere in this file: a * b + c stays two roundings unless written fmaf. HIP's __fmul_rn / __fadd_rn
+// are plain operators that the compiler may still fuse after inlining (it did, in one instantiation of the post kernel
+// and not in another), so the single-rounding operations are spelled out here, under the pragma.
+#pragma clang fp contract(off)
+
+namespace {
+
+__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
+__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
+__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
+__device__ __forceinline__ float div_rn(float a, float b) { return a / b; }
+
+int live_grid(long long work) {
+    long long g = (work + 255) / 256;
+    if (g > 16384) g = 16384;
+    return (int)(g < 1 ? 1 : g);
+}
+
+__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < INFINITY; }  // false for NaN
+
+// V consecutive elements per thread in the plane-streaming kernels (post, contours, auto-range codes): V = 4 when the
+// element count is a multiple of 4 and the pointers are aligned (16-B float and 4-B byte-plane accesses), else V = 1.
+// The gathering kernels (front end, rectified view, compose) stay one pixel per thread: four pixels per thread with
+// 12-B BGR stores measured slower (rectify 4.7 -> 7.2 us, compose 6.1 -> 7.2 us at 640x480: a quarter of the threads,
+// each with four times the dependent gather latency).
+template <int V> __device__ __forceinline__ void ld_f(const float* p, float (&v)[V]) {
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        v[0] = p[0];
+    }
+}
+template <int V> __device__ __forceinline__ void st_f(float* p, const float (&v)[V]) {
+    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else p[0] = v[0];
+}
+__device__ __forceinline__ uint32_t pack4(uint8_t a, uint8_t b, uint8_t c, uint8_t d) {
+    return (uint32_t)a | (uint32_t)b << 8 | (uint32_t)c << 16 | (uint32_t)d << 24;
+}
+template <int V> __device__ __forceinline__ void st_u8(uint8_t* p, const uint8_t (&v)[V]) {
+    if constexpr (V == 4) *reinterpret_cast<uint32_t*>(p) = pack4(v[0], v[1], v[2], v[3]);
+    else p[0] = v[0];
+}
+bool aligned(const void* p, unsigned a) { return ((uintptr_t)p % a) == 0; }  // NULL counts as aligned
+
+// ------------------------------------------------------------------ front end
+// Remapped pixel (y, x) of one BGR frame, values in [0, 255]. map1 int16 [Hc][Wc][2] = integer x, y; map2 uint16
+// [Hc][Wc], low 10 bits = fy5 << 5 | fx5 (fractions in 1/32 px): OpenCV's CV_16SC2 fixed-point maps. Bilinear, a tap
+// outside the frame contributes 0. Weights are multiples of 1/32 and taps are bytes: every product and sum below is
+// exact in fp32. map1 == NULL: the frame itself.
+__device__ __forceinline__ void remap_px(const uint8_t* __restrict__ img, int Hc, int Wc, const short* __restrict__ map1,
+                                         const unsigned short* __restrict__ map2, int y, int x, float (&v)[3]) {
+    const size_t p = (size_t)y * Wc + x;
+    if (!map1) {
+        const uint8_t* q = img + p * 3;
+        v[0] = (float)q[0];
+        v[1] = (float)q[1];
+        v[2] = (float)q[2];
+        return;
+    }
+    const int ix = map1[2 * p], iy = map1[2 * p + 1];
+    const unsigned f = map2[p];
+    const float fx = (float)(f & 31u) * (1.f / 32.f), fy = (float)((f >> 5) & 31u) * (1.f / 32.f);
+    float t[2][2][3];
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            const int yy = iy + dy, xx = ix + dx;
+            const bool in = (unsigned)yy < (unsigned)Hc && (unsigned)xx < (unsigned)Wc;
+            const uint8_t* q = img + ((size_t)(in ? yy : 0) * Wc + (in ? xx : 0)) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) t[dy][dx][c] = in ? (float)q[c] : 0.f;
+        }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float top = fmaf(fx, sub_rn(t[0][1][c], t[0][0][c]), t[0][0][c]);
+        const float bot = fmaf(fx, sub_rn(t[1][1][c], t[1][0][c]), t[1][0][c]);
+        v[c] = fmaf(fy, sub_rn(bot, top), top);
+    }
+}
+
+// Model-resolution pixel (y, x) of one frame: bilinear resize (half-pixel centres, edge replicate: src_index) taken over
+// the REMAPPED image (up to 16 source taps per channel), / 255, in RGB order. The one place this value is computed.
+__device__ __forceinline__ void live_px(const uint8_t* __restrict__ img, int Hc, int Wc, const short* __restrict__ map1,
+                                        const unsigned short* __restrict__ map2, int H, int W, int y, int x,
+                                        float (&rgb)[3]) {
+    int y0, y1, x0, x1;
+    float ly, lx;
+    src_index(y, H, Hc, y0, y1, ly);
+    src_index(x, W, Wc, x0, x1, lx);
+    float a[3], b[3], c[3], d[3];
+    remap_px(img, Hc, Wc, map1, map2, y0, x0, a);
+    remap_px(img, Hc, Wc, map1, map2, y0, x1, b);
+    remap_px(img, Hc, Wc, map1, map2, y1, x0, c);
+    remap_px(img, Hc, Wc, map1, map2, y1, x1, d);
+    const float wx = sub_rn(1.f, lx), wy = sub_rn(1.f, ly);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float top = fmaf(b[ch], lx, mul_rn(a[ch], wx));
+        const float bot = fmaf(d[ch], lx, mul_rn(c[ch], wx));
+        rgb[2 - ch] = div_rn(fmaf(bot, ly, mul_rn(top, wy)), 255.f);
+    }
+}
+
+// one model pixel per thread: 8-channel NHWC vector store [L_R, L_G, L_B, R_R, R_G, R_B, 0, 0], optional NCHW planes,
+// optional max over the frame into amax[slot] with amax[clear] zeroed (the protocol of k_pack_input_amax, misc.hip)
+template <typename T>
+__global__ __launch_bounds__(256) void k_live_frontend(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                                       int Hc, int Wc, const short* __restrict__ m1l,
+                                                       const unsigned short* __restrict__ m2l,
+                                                       const short* __restrict__ m1r,
+                                                       const unsigned short* __restrict__ m2r, int H, int W,
+                                                       T* __restrict__ xin, float* __restrict__ nchw, unsigned* amax,
+                                                       int slot, int clear) {
+    const int P = H * W;
+    float m = 0.f;
+    for (int px = blockIdx.x * 256 + threadIdx.x; px < P; px += gridDim.x * 256) {
+        const int y = px / W, x = px - y * W;
+        float l[3], r[3];
+        live_px(left, Hc, Wc, m1l, m2l, H, W, y, x, l);
+        live_px(right, Hc, Wc, m1r, m2r, H, W, y, x, r);
+        const float v[8] = {l[0], l[1], l[2], r[0], r[1], r[2], 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) m = fmaxf(m, fabsf(v[i]));
+        store8(xin + (size_t)px * 8, v);
+        if (nchw) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) nchw[(size_t)i * P + px] = v[i];
+        }
+    }
+    if (amax) {  // uniform over the grid
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        __shared__ float wm[4];
+        if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned mb = __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3])));
+            if (mb > __hip_atomic_load(amax + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(amax + slot, mb);
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 64 && clear >= 0) amax[clear] = 0u;
+    }
+}
+
+// the rectified view as the display shows it: remapped BGR bytes, round half to even (the value is a multiple of 1/1024)
+__global__ __launch_bounds__(256) void k_live_rectify(const uint8_t* __restrict__ img, int Hc, int Wc,
+                                                      const short* __restrict__ map1,
+                                                      const unsigned short* __restrict__ map2, uint8_t* __restrict__ view) {
+    const int P = Hc * Wc;
+    for (int px = blockIdx.x * 256 + threadIdx.x; px < P; px += gridDim.x * 256) {
+        const int y = px / Wc, x = px - y * Wc;
+        float v[3];
+        remap_px(img, Hc, Wc, map1, map2, y, x, v);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) view[(size_t)px * 3 + c] = (uint8_t)min(max(__float2int_rn(v[c]), 0), 255);
+    }
+}
+
+// ------------------------------------------------------------------ post stage
+// colorize_scalar_map's uint8 code: trunc(clip((v - lo) / scale, 0, 1) * 255) for finite v > 0, else 0
+__device__ __forceinline__ uint8_t code_of(float v, float lo, float scale) {
+    if (!(finite_f(v) && v > 0.f)) return 0;
+    const float t = fminf(fmaxf(div_rn(sub_rn(v, lo), scale), 0.f), 1.f);
+    return (uint8_t)(int)mul_rn(t, 255.f);
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_live_post(const float* __restrict__ pred, const float* __restrict__ logvar, int P,
+                                                   float* __restrict__ state, int copy, float a, float b, int depth_on,
+                                                   float fb, float* __restrict__ depth, float* __restrict__ conf,
+                                                   uint8_t* __restrict__ dcode, float dlo, float dscale,
+                                                   uint8_t* __restrict__ ccode, float clo, float cscale) {
+    for (int i = (blockIdx.x * 256 + threadIdx.x) * V; i < P; i += gridDim.x * 256 * V) {
+        float s[V];
+        ld_f<V>(pred + i, s);
+        if (!copy) {
+            float o[V];
+            ld_f<V>(state + i, o);
+#pragma unroll
+            for (int k = 0; k < V; ++k) s[k] = add_rn(mul_rn(a, s[k]), mul_rn(b, o[k]));
+        }
+        st_f<V>(state + i, s);
+        if (depth_on) {
+            float d[V];
+            uint8_t c[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                d[k] = (finite_f(s[k]) && s[k] > 1e-6f) ? div_rn(fb, s[k]) : NAN;
+                c[k] = code_of(d[k], dlo, dscale);
+            }
+            st_f<V>(depth + i, d);
+            if (dcode) st_u8<V>(dcode + i, c);
+        }
+        if (logvar) {
+            float l[V];
+            uint8_t c[V];
+            ld_f<V>(logvar + i, l);
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                l[k] = expf(mul_rn(-0.5f, l[k]));
+                c[k] = code_of(l[k], clo, cscale);
+            }
+            st_f<V>(conf + i, l);
+            if (ccode) st_u8<V>(ccode + i, c);
+        }
+    }
+}
+
+// depth_contour_mask: 255 where the right or the lower neighbour is valid too and lies in another depth bin
+__device__ __forceinline__ int contour_bin(float d, float dmin, float dmax, float step) {
+    if (!(finite_f(d) && d > dmin && d <= dmax)) return -1;
+    return (int)floorf(div_rn(sub_rn(fminf(fmaxf(d, dmin), dmax), dmin), step));
+}
+// V = 4 needs W % 4 == 0: the four pixels of a thread then lie in one row
+template <int V>
+__global__ __launch_bounds__(256) void k_live_edges(const float* __restrict__ depth, int H, int W, float dmin, float dmax,
+                                                    float step, uint8_t* __restrict__ edge) {
+    const int P = H * W;
+    for (int i = (blockIdx.x * 256 + threadIdx.x) * V; i < P; i += gridDim.x * 256 * V) {
+        const int y = i / W, x = i - y * W;
+        float d[V], dn[V];
+        ld_f<V>(depth + i, d);
+        const bool below = y + 1 < H;
+        if (below) ld_f<V>(depth + i + W, dn);
+        int b[V + 1];
+#pragma unroll
+        for (int k = 0; k < V; ++k) b[k] = contour_bin(d[k], dmin, dmax, step);
+        b[V] = x + V < W ? contour_bin(depth[i + V], dmin, dmax, step) : -1;
+        uint8_t e[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            bool on = b[k] >= 0 && b[k + 1] >= 0 && b[k + 1] != b[k];
+            if (below && b[k] >= 0) {
+                const int q = contour_bin(dn[k], dmin, dmax, step);
+                on |= q >= 0 && q != b[k];
+            }
+            e[k] = on ? 255 : 0;
+        }
+        st_u8<V>(edge + i, e);
+    }
+}
+
+// ------------------------------------------------------------------ exact order statistics (auto range)
+// Finite positive floats order like their bit patterns (< 0x7f800000, 31 bits): a three-level radix select, 11 + 11 + 9
+// bits. Level 1 histograms the top 11 bits of every valid value; a one-block scan finds, for each of the four wanted
+// ranks, the bin that holds it and the rank within the bin; level 2 histograms the next 11 bits of the values in those
+// bins, level 3 the last 9. Targets that share a prefix share a histogram. Histograms are built in LDS per block and
+// added to the global ones (non-zero bins only). The last scan writes the results and zeroes the work buffer again.
+constexpr int SEL_H1 = 0, SEL_H2 = 2048, SEL_H3 = SEL_H2 + 4 * 2048, SEL_STATE = SEL_H3 + 4 * 512;
+constexpr int SEL_WORDS = SEL_STATE + 16;  // state: n, prefix[4], rank[4]
+
+template <int LEVEL>
+__global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ v, int P, unsigned* __restrict__ work) {
+    constexpr int BINS = LEVEL == 3 ? 512 : 2048, NH = LEVEL == 1 ? 1 : 4;
+    __shared__ unsigned h[NH * BINS];
+    for (int i = threadIdx.x; i < NH * BINS; i += 256) h[i] = 0u;
+    unsigned pf[4] = {0u, 0u, 0u, 0u};
+    bool own[4] = {true, false, false, false};
+    if (LEVEL > 1) {
+        if (work[SEL_STATE] == 0u) return;  // no valid value (uniform)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pf[j] = work[SEL_STATE + 1 + j];
+#pragma unroll
+        for (int j = 1; j < 4; ++j) own[j] = pf[j] != pf[j - 1];
+    }
+    __syncthreads();
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < P; i += gridDim.x * 256) {
+        const float x = v[i];
+        if (!(finite_f(x) && x > 0.f)) continue;
+        const unsigned key = __float_as_uint(x);
+        if (LEVEL == 1) {
+            atomicAdd(&h[key >> 20], 1u);
+        } else {
+            const unsigned hi = LEVEL == 2 ? key >> 20 : key >> 9;
+            const unsigned lo = LEVEL == 2 ? (key >> 9) & 2047u : key & 511u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (own[j] && hi == pf[j]) atomicAdd(&h[j * BINS + lo], 1u);
+        }
+    }
+    __syncthreads();
+    unsigned* g = work + (LEVEL == 1 ? SEL_H1 : LEVEL == 2 ? SEL_H2 : SEL_H3);
+    for (int i = threadIdx.x; i < NH * BINS; i += 256)
+        if (h[i]) atomicAdd(g + i, h[i]);
+}
+
+// numpy's `linear` percentile of the sorted valid values from the two order statistics around (n - 1) * q, in fp64
+// (lib/_function_base_impl.py: _lerp), rounded to float32 once
+__device__ __forceinline__ float lerp_q(float a, float b, double vi) {
+    const double g = vi - floor(vi), d = (double)b - (double)a;
+    return (float)(g >= 0.5 ? (double)b - d * (1.0 - g) : (double)a + d * g);
+}
+
+template <int LEVEL>
+__global__ __launch_bounds__(256) void k_sel_scan(unsigned* __restrict__ work, float* __restrict__ sel) {
+    constexpr int BINS = LEVEL == 3 ? 512 : 2048, PER = BINS / 256, BITS = LEVEL == 3 ? 9 : 11;
+    unsigned* st = work + SEL_STATE;
+    __shared__ unsigned part[4][256];
+    __shared__ unsigned s_pf[4], s_rk[4], s_out[4], s_n;
+    const int t = threadIdx.x;
+    if (t < 4) {
+        s_pf[t] = LEVEL == 1 ? 0u : st[1 + t];
+        s_rk[t] = LEVEL == 1 ? 0u : st[5 + t];
+    }
+    if (t == 0) s_n = LEVEL == 1 ? 0u : st[0];
+    __syncthreads();
+    const unsigned* hist[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int src = j;
+        if (LEVEL > 1)
+            while (src > 0 && s_pf[src] == s_pf[src - 1]) --src;
+        hist[j] = LEVEL == 1 ? work + SEL_H1 : work + (LEVEL == 2 ? SEL_H2 : SEL_H3) + src * BINS;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        unsigned sum = 0u;
+        for (int i = 0; i < PER; ++i) sum += hist[j][t * PER + i];
+        part[j][t] = sum;
+    }
+    __syncthreads();
+    if (LEVEL == 1 && t == 0) {
+        unsigned n = 0u;
+        for (int c = 0; c < 256; ++c) n += part[0][c];
+        s_n = n;
+        if (n > 0u) {
+            const unsigned klo = (unsigned)floor((double)(n - 1u) * 0.02), khi = (unsigned)floor((double)(n - 1u) * 0.98);
+            s_rk[0] = klo;
+            s_rk[1] = min(klo + 1u, n - 1u);
+            s_rk[2] = khi;
+            s_rk[3] = min(khi + 1u, n - 1u);
+        }
+    }
+    __syncthreads();
+    const unsigned n = s_n;
+    if (t < 4 && n > 0u) {
+        const unsigned r = s_rk[t];
+        unsigned cum = 0u;
+        int c = 0;
+        while (c < 255 && cum + part[t][c] <= r) cum += part[t][c++];
+        int b = c * PER;
+        while (b < c * PER + PER - 1 && cum + hist[t][b] <= r) cum += hist[t][b++];
+        s_out[t] = (s_pf[t] << BITS) | (unsigned)b;
+        st[1 + t] = s_out[t];
+        st[5 + t] = r - cum;
+    }
+    if (t == 0) st[0] = n;
+    if (LEVEL == 3) {
+        __syncthreads();  // the histograms were read: zero the whole work buffer for the next call
+        for (int i = t; i < SEL_WORDS; i += 256) work[i] = 0u;
+        if (t == 0) {
+            unsigned* seln = reinterpret_cast<unsigned*>(sel);
+            seln[0] = n;
+            if (n == 0u) {
+                for (int j = 1; j < 7; ++j) sel[j] = NAN;
+            } else {
+                const float a0 = __uint_as_float(s_out[0]), a1 = __uint_as_float(s_out[1]);
+                const float b0 = __uint_as_float(s_out[2]), b1 = __uint_as_float(s_out[3]);
+                sel[1] = a0;
+                sel[2] = a1;
+                sel[3] = b0;
+                sel[4] = b1;
+                sel[5] = lerp_q(a0, a1, (double)(n - 1u) * 0.02);
+                sel[6] = lerp_q(b0, b1, (double)(n - 1u) * 0.98);
+            }
+        }
+    }
+}
+
+// the auto-range codes: lo, hi and n from sd_live_select's result, on the device; scale = max(hi - lo, 1e-6) in fp64
+template <int V>
+__global__ __launch_bounds__(256) void k_live_code_auto(const float* __restrict__ v, int P, const float* __restrict__ sel,
+                                                        uint8_t* __restrict__ code) {
+    const unsigned n = reinterpret_cast<const unsigned*>(sel)[0];
+    const float lo = sel[5];
+    const float scale = (float)fmax((double)sel[6] - (double)sel[5], 1e-6);
+    for (int i = (blockIdx.x * 256 + threadIdx.x) * V; i < P; i += gridDim.x * 256 * V) {
+        float x[V];
+        uint8_t c[V];
+        ld_f<V>(v + i, x);
+#pragma unroll
+        for (int k = 0; k < V; ++k) c[k] = n ? code_of(x[k], lo, scale) : 0;
+        st_u8<V>(code + i, c);
+    }
+}
+
+// ------------------------------------------------------------------ centre-window medians
+// block b: the median of the finite, > 0 values of map b's centre window (bounds as depth_live_dl.py:542-548), by a
+// bitonic sort of the window in LDS (<= 63 x 63 values, padded with +inf to a power of two). Even count: the fp32 mean
+// of the two middle values (numpy's median); empty: NaN.
+__global__ __launch_bounds__(256) void k_live_center(const float* m0, const float* m1, const float* m2, int H, int W,
+                                                     int window, float* __restrict__ out) {
+    const float* src = blockIdx.x == 0 ? m0 : blockIdx.x == 1 ? m1 : m2;
+    if (!src) {
+        if (threadIdx.x == 0) out[blockIdx.x] = NAN;
+        return;
+    }
+    __shared__ float buf[4096];
+    __shared__ int s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    const int cx = W / 2, cy = H / 2, half = max(1, window / 2);
+    const int y0 = max(0, cy - half), y1 = min(H, cy + half + 1), x0 = max(0, cx - half), x1 = min(W, cx + half + 1);
+    const int ww = x1 - x0, total = (y1 - y0) * ww;
+    int n2 = 64;
+    while (n2 < total) n2 <<= 1;
+    __syncthreads();
+    int mine = 0;
+    for (int i = threadIdx.x; i < n2; i += 256) {
+        float x = INFINITY;
+        if (i < total) {
+            const int r = i / ww;
+            x = src[(size_t)(y0 + r) * W + x0 + (i - r * ww)];
+            if (finite_f(x) && x > 0.f) ++mine;
+            else x = INFINITY;
+        }
+        buf[i] = x;
+    }
+    if (mine) atomicAdd(&s_cnt, mine);
+    __syncthreads();
+    for (int k = 2; k <= n2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < n2; i += 256) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const float a = buf[i], b = buf[l];
+                    if ((a > b) == ((i & k) == 0)) {
+                        buf[i] = b;
+                        buf[l] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    if (threadIdx.x == 0) {
+        const int m = s_cnt;
+        out[blockIdx.x] = m == 0 ? NAN : (m & 1) ? buf[m / 2] : div_rn(add_rn(buf[m / 2 - 1], buf[m / 2]), 2.f);
+    }
+}
+
+// ------------------------------------------------------------------ compose
+// One view pixel per thread. Each colour image: the [256][3] BGR LUT applied to the model-resolution codes, resized
+// bilinearly to the view (half-pixel centres, edge replicate, round half to even), i.e. cv2.resize(applyColorMap(code)).
+// The contour mask is nearest-resized (sx = min(dx * Ws / Wd, Ws - 1)) and painted (0, 255, 0) onto the left view.
+__device__ __forceinline__ void lut_bilerp(const uint8_t* __restrict__ code, const uint8_t* lut, int W, int y0, int y1,
+                                           int x0, int x1, float ly, float lx, uint8_t* out) {
+    const uint8_t* a = lut + 3 * code[(size_t)y0 * W + x0];
+    const uint8_t* b = lut + 3 * code[(size_t)y0 * W + x1];
+    const uint8_t* c = lut + 3 * code[(size_t)y1 * W + x0];
+    const uint8_t* d = lut + 3 * code[(size_t)y1 * W + x1];
+    const float wx = sub_rn(1.f, lx), wy = sub_rn(1.f, ly);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float top = fmaf((float)b[ch], lx, mul_rn((float)a[ch], wx));
+        const float bot = fmaf((float)d[ch], lx, mul_rn((float)c[ch], wx));
+        out[ch] = (uint8_t)min(max(__float2int_rn(fmaf(bot, ly, mul_rn(top, wy))), 0), 255);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_live_compose(const uint8_t* __restrict__ code_a, const uint8_t* __restrict__ lut_a,
+                                                      uint8_t* __restrict__ vis_a, const uint8_t* __restrict__ code_b,
+                                                      const uint8_t* __restrict__ lut_b, uint8_t* __restrict__ vis_b,
+                                                      const uint8_t* __restrict__ edge, const uint8_t* __restrict__ view,
+                                                      uint8_t* __restrict__ left_view, int H, int W, int Hc, int Wc) {
+    __shared__ uint8_t lut[2][768];
+    for (int i = threadIdx.x; i < 768; i += 256) {
+        lut[0][i] = code_a ? lut_a[i] : 0;
+        lut[1][i] = code_b ? lut_b[i] : 0;
+    }
+    __syncthreads();
+    const int P = Hc * Wc;
+    for (int px = blockIdx.x * 256 + threadIdx.x; px < P; px += gridDim.x * 256) {
+        const int dy = px / Wc, dx = px - dy * Wc;
+        if (code_a || code_b) {
+            int y0, y1, x0, x1;
+            float ly, lx;
+            src_index(dy, Hc, H, y0, y1, ly);
+            src_index(dx, Wc, W, x0, x1, lx);
+            if (code_a) lut_bilerp(code_a, lut[0], W, y0, y1, x0, x1, ly, lx, vis_a + (size_t)px * 3);
+            if (code_b) lut_bilerp(code_b, lut[1], W, y0, y1, x0, x1, ly, lx, vis_b + (size_t)px * 3);
+        }
+        if (left_view) {
+            bool on = false;
+            if (edge) {
+                const int sy = min((int)((long long)dy * H / Hc), H - 1), sx = min((int)((long long)dx * W / Wc), W - 1);
+                on = edge[(size_t)sy * W + sx] != 0;
+            }
+            const uint8_t* q = view + (size_t)px * 3;
+            uint8_t* o = left_view + (size_t)px * 3;
+            o[0] = on ? 0 : q[0];
+            o[1] = on ? 255 : q[1];
+            o[2] = on ? 0 : q[2];
+        }
+    }
+}
+
+bool live_dims_ok(int H, int W) { return H > 0 && W > 0 && (long long)H * W <= INT_MAX / 16; }
+
+}  // namespace
+
+extern "C" int sd_live_frontend(int dtype, const uint8_t* left, const uint8_t* right, int Hc, int Wc,
+                                const int16_t* map1_l, const uint16_t* map2_l, const int16_t* map1_r,
+                                const uint16_t* map2_r, int H, int W, void* xin, float* nchw, unsigned* amax, int slot,
+                                int clear, sd_stream s) {
+    SD_REQUIRE(left && right && xin, "sd_live_frontend: null pointer");
+    SD_REQUIRE(live_dims_ok(Hc, Wc) && live_dims_ok(H, W), "sd_live_frontend: bad sizes %dx%d -> %dx%d", Hc, Wc, H, W);
+    SD_REQUIRE(!map1_l == !map2_l && !map1_r == !map2_r, "sd_live_frontend: map1 and map2 go together");
+    SD_REQUIRE(dtype == SD_F32 || dtype == SD_BF16, "sd_live_frontend: dtype %d", dtype);
+    SD_REQUIRE((uintptr_t)xin % 16 == 0, "sd_live_frontend: xin must be 16-B aligned");
+    SD_REQUIRE(!amax || (slot >= 0 && clear != slot), "sd_live_frontend: amax slot %d clear %d", slot, clear);
+    const dim3 g(live_grid((long long)H * W));
+    if (dtype == SD_BF16)
+        hipLaunchKernelGGL(k_live_frontend<__bf16>, g, dim3(256), 0, to_stream(s), left, right, Hc, Wc, map1_l, map2_l,
+                           map1_r, map2_r, H, W, (__bf16*)xin, nchw, amax, slot, clear);
+    else
+        hipLaunchKernelGGL(k_live_frontend<float>, g, dim3(256), 0, to_stream(s), left, right, Hc, Wc, map1_l, map2_l,
+                           map1_r, map2_r, H, W, (float*)xin, nchw, amax, slot, clear);
+    return sd_check_launch("sd_live_frontend");
+}
+
+extern "C" int sd_live_rectify(const uint8_t* frame, int Hc, int Wc, const int16_t* map1, const uint16_t* map2,
+                               uint8_t* view, sd_stream s) {
+    SD_REQUIRE(frame && view && map1 && map2, "sd_live_rectify: null pointer");
+    SD_REQUIRE(live_dims_ok(Hc, Wc), "sd_live_rectify: bad sizes %dx%d", Hc, Wc);
+    hipLaunchKernelGGL(k_live_rectify, dim3(live_grid((long long)Hc * Wc)), dim3(256), 0, to_stream(s), frame, Hc, Wc,
+                       map1, map2, view);
+    return sd_check_launch("sd_live_rectify");
+}
+
+extern "C" int sd_live_post(const float* disp, const float* logvar, int H, int W, float* state, int copy, float alpha,
+                            float one_minus_alpha, int depth_on, float focal_baseline, float* depth, float* conf,
+                            uint8_t* depth_code, float depth_lo, float depth_scale, uint8_t* conf_code, float conf_lo,
+                            float conf_scale, sd_stream s) {
+    SD_REQUIRE(disp && state, "sd_live_post: null pointer");
+    SD_REQUIRE(live_dims_ok(H, W), "sd_live_post: bad sizes %dx%d", H, W);
+    SD_REQUIRE(!depth_on || depth, "sd_live_post: depth enabled without a depth buffer");
+    SD_REQUIRE(!logvar || conf, "sd_live_post: logvar without a confidence buffer");
+    SD_REQUIRE((!depth_code || depth_scale > 0.f) && (!conf_code || conf_scale > 0.f), "sd_live_post: code scale <= 0");
+    const int P = H * W;
+    const bool vec = P % 4 == 0 && aligned(disp, 16) && aligned(logvar, 16) && aligned(state, 16) && aligned(depth, 16) &&
+                     aligned(conf, 16) && aligned(depth_code, 4) && aligned(conf_code, 4);
+    hipLaunchKernelGGL(vec ? k_live_post<4> : k_live_post<1>, dim3(live_grid(vec ? P / 4 : P)), dim3(256), 0, to_stream(s),
+                       disp, logvar, P, state, copy, alpha, one_minus_alpha, depth_on, focal_baseline, depth, conf,
+                       depth_code, depth_lo, depth_scale, conf_code, conf_lo, conf_scale);
+    return sd_check_launch("sd_live_post");
+}
+
+extern "C" int sd_live_contours(const float* depth, int H, int W, float min_depth, float max_depth, float step,
+                                uint8_t* edge, sd_stream s) {
+    SD_REQUIRE(depth && edge, "sd_live_contours: null pointer");
+    SD_REQUIRE(live_dims_ok(H, W), "sd_live_contours: bad sizes %dx%d", H, W);
+    SD_REQUIRE(step > 0.f && max_depth > min_depth, "sd_live_contours: bad range");
+    const bool vec = W % 4 == 0 && aligned(depth, 16) && aligned(edge, 4);
+    hipLaunchKernelGGL(vec ? k_live_edges<4> : k_live_edges<1>, dim3(live_grid((long long)H * W / (vec ? 4 : 1))), dim3(256),
+                       0, to_stream(s), depth, H, W, min_depth, max_depth, step, edge);
+    return sd_check_launch("sd_live_contours");
+}
+
+extern "C" long long sd_live_select_ws_bytes(void) { return (long long)SEL_WORDS * 4; }
+
+extern "C" int sd_live_select(const float* values, int H, int W, unsigned* work, float* sel, uint8_t* code,
+                              sd_stream s) {
+    SD_REQUIRE(values && work && sel, "sd_live_select: null pointer");
+    SD_REQUIRE(live_dims_ok(H, W), "sd_live_select: bad sizes %dx%d", H, W);
+    const int P = H * W;
+    const dim3 g(cdiv(P, 1024) < 256 ? cdiv(P, 1024) : 256), b(256);
+    hipStream_t st = to_stream(s);
+    hipLaunchKernelGGL(k_sel_hist<1>, g, b, 0, st, values, P, work);
+    hipLaunchKernelGGL(k_sel_scan<1>, dim3(1), b, 0, st, work, sel);
+    hipLaunchKernelGGL(k_sel_hist<2>, g, b, 0, st, values, P, work);
+    hipLaunchKernelGGL(k_sel_scan<2>, dim3(1), b, 0, st, work, sel);
+    hipLaunchKernelGGL(k_sel_hist<3>, g, b, 0, st, values, P, work);
+    hipLaunchKernelGGL(k_sel_scan<3>, dim3(1), b, 0, st, work, sel);
+    if (code) {
+        const bool vec = P % 4 == 0 && aligned(values, 16) && aligned(code, 4);
+        hipLaunchKernelGGL(vec ? k_live_code_auto<4> : k_live_code_auto<1>, dim3(live_grid(vec ? P / 4 : P)), b, 0, st,
+                           values, P, sel, code);
+    }
+    return sd_check_launch("sd_live_select");
+}
+
+extern "C" int sd_live_center(const float* disp, const float* depth, const float* conf, int H, int W, int window,
+                              float* out3, sd_stream s) {
+    SD_REQUIRE(disp && out3, "sd_live_center: null pointer");
+    SD_REQUIRE(live_dims_ok(H, W), "sd_live_center: bad sizes %dx%d", H, W);
+    SD_REQUIRE(window >= 0 && window <= 63, "sd_live_center: window %d (max 63)", window);
+    hipLaunchKernelGGL(k_live_center, dim3(3), dim3(256), 0, to_stream(s), disp, depth, conf, H, W, window, out3);
+    return sd_check_launch("sd_live_center");
+}
+
+extern "C" int sd_live_compose(const uint8_t* code_a, const uint8_t* lut_a, uint8_t* vis_a, const uint8_t* code_b,
+                               const uint8_t* lut_b, uint8_t* vis_b, const uint8_t* edge, const uint8_t* view,
+                               uint8_t* left_view, int H, int W, int Hc, int Wc, sd_stream s) {
+    SD_REQUIRE(code_a || code_b || left_view, "sd_live_compose: nothing to do");
+    SD_REQUIRE(!code_a || (lut_a && vis_a), "sd_live_compose: null pointer (image a)");
+    SD_REQUIRE(!code_b || (lut_b && vis_b), "sd_live_compose: null pointer (image b)");
+    SD_REQUIRE(!left_view || view, "sd_live_compose: null pointer (view)");
+    SD_REQUIRE(!edge || left_view, "sd_live_compose: contour mask without a left view to paint");
+    SD_REQUIRE(live_dims_ok(H, W) && live_dims_ok(Hc, Wc), "sd_live_compose: bad sizes %dx%d -> %dx%d", H, W, Hc, Wc);
+    hipLaunchKernelGGL(k_live_compose, dim3(live_grid((long long)Hc * Wc)), dim3(256), 0, to_stream(s), code_a, lut_a, vis_a,
+                       code_b, lut_b, vis_b, edge, view, left_view, H, W, Hc, Wc);
+    return sd_check_launch("sd_live_compose");
+}

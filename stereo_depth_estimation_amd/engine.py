@@ -767,6 +767,43 @@ class UNetEngine:
         B, C, H, W = x.shape
         if C != self.in_channels:
             raise ValueError(f"expected {self.in_channels} input channels, got {C}")
+
+        def pack(ws):
+            xc = x.contiguous().float()
+            ready, self._xin_ready = getattr(self, "_xin_ready", None), None
+            if ready is not None and ready == (xc.data_ptr(), tuple(xc.shape), ws.t["xin"].data_ptr()):
+                pass  # packed by step_prologue
+            elif self.fp8 and self.fp8_static and self._q8_shapes:
+                self._pack_input_fp8(ws, lambda amax, slot, clear: L.call(
+                    "sd_pack_input_amax", self.sd_dtype, xc.data_ptr(), B, C, H, W, self.cin_pad0,
+                    ws.t["xin"].data_ptr(), amax, slot, clear, self._s()))
+            else:
+                L.call("sd_pack_input", self.sd_dtype, xc.data_ptr(), B, C, H, W, self.cin_pad0,
+                       ws.t["xin"].data_ptr(), self._s())
+
+        return self._forward(B, H, W, train, need_backward, pack)
+
+    def forward_packed(self, H: int, W: int, pack):
+        """An eval forward (B = 1, no backward) whose input the caller packs itself: pack(xin_ptr, amax_ptr, slot,
+        clear, stream) must fill the workspace's NHWC input (cin_pad0 channels, the engine's dtype) on `stream`, as
+        sd_pack_input would, and, when amax_ptr is not None, follow sd_pack_input_amax's protocol for amax[slot] /
+        amax[clear] (the static fp8 path's range check; otherwise slot = 0, clear = -1). Everything after the pack,
+        graph replay included, is forward()'s."""
+        if self.in_channels > self.cin_pad0:
+            raise ValueError("forward_packed: the model's input does not fit the packed layout")
+
+        def feed(ws):
+            self._xin_ready = None
+            xin = ws.t["xin"].data_ptr()
+            if self.fp8 and self.fp8_static and self._q8_shapes:
+                self._pack_input_fp8(ws, lambda amax, slot, clear: pack(xin, amax, slot, clear, self._s()))
+            else:
+                pack(xin, None, 0, -1, self._s())
+
+        return self._forward(1, H, W, False, False, feed)
+
+    def _forward(self, B: int, H: int, W: int, train: bool, need_backward: bool | None, pack):
+        """forward() after the input checks; pack(ws) fills ws.t["xin"]."""
         if self.fp8 and train:
             raise RuntimeError("precision='fp8' is the inference-only forward (BASELINE config 5): call model.eval()")
         if need_backward is None:
@@ -785,15 +822,7 @@ class UNetEngine:
             self._eval_coeffs = key is None or ws.coeff_key != key
             ws.coeff_key = key
         self.phase = "fwd"  # read by measurement hooks (bench.py) to tell forward from backward launches
-        x = x.contiguous().float()
-        ready, self._xin_ready = getattr(self, "_xin_ready", None), None
-        if ready is not None and ready == (x.data_ptr(), tuple(x.shape), ws.t["xin"].data_ptr()):
-            pass  # packed by step_prologue
-        elif self.fp8 and self.fp8_static and self._q8_shapes:
-            self._pack_input_fp8(ws, x)
-        else:
-            L.call("sd_pack_input", self.sd_dtype, x.data_ptr(), B, C, H, W, self.cin_pad0, ws.t["xin"].data_ptr(),
-                   self._s())
+        pack(ws)
         # eval forwards of an unchanged model state (the live app's loop): the launches after the input pack are
         # captured into a HIP graph on the second such forward and replayed from the third on (one host call instead
         # of 27-45 ctypes launches; B=1 960x720 forwards were host-bound at ~20 us of GPU time per kernel)
@@ -864,11 +893,11 @@ class UNetEngine:
         self._fp8_age += 1
         return False
 
-    def _pack_input_fp8(self, ws: Workspace, x: torch.Tensor):
-        """The static-scale fp8 path's input pack: sd_pack_input + the input amax for _fp8_policy. A ring of three
+    def _pack_input_fp8(self, ws: Workspace, launch):
+        """The static-scale fp8 path's input pack: launch(amax_ptr, slot, clear) packs the input and takes its amax
+        for _fp8_policy (sd_pack_input_amax, or the live front end through forward_packed). A ring of three
         device words: frame f takes word f % 3 and zeroes word (f + 1) % 3, after the launch stream has waited for the
         side-stream read-back of that word (frame f - 2's, long complete: a barrier packet, no stall)."""
-        B, C, H, W = x.shape
         slot = self._fp8_frame % 3
         clear = (slot + 1) % 3
         self._fp8_frame += 1
@@ -889,8 +918,7 @@ class UNetEngine:
         main = torch.cuda.current_stream(self.device)
         if self._amax_used[clear]:
             main.wait_event(self._amax_ev[clear])
-        L.call("sd_pack_input_amax", self.sd_dtype, x.data_ptr(), B, C, H, W, self.cin_pad0, ws.t["xin"].data_ptr(),
-               self._amax_dev.data_ptr(), slot, clear, self._s())
+        launch(self._amax_dev.data_ptr(), slot, clear)
         self._amax_packed.record(main)
         self._amax_pending = slot  # read back by _amax_readback once the forward's launches are queued
         if not ws.q8_ready:

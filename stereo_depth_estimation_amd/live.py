@@ -1,0 +1,369 @@
+"""The live depth loop's frame path on the device (the reference's live_camera/depth_live_dl.py:468-617 around
+``model(x)``): raw uint8 BGR camera frames in, display-ready uint8 images and three centre scalars out.
+
+    live = LiveDepth(model, model_size=(960, 720), rectification=rect)
+    res = live.step(frame_l, frame_r)        # no host sync: device tensors, overwritten by the next step
+    center_disp, center_depth_m, center_conf = res.readout()   # the only host sync
+
+Rectification (cv2.remap with OpenCV's fixed-point maps), BGR->RGB, resize, /255 and the engine's input pack are one
+HIP pass that writes the engine's input; EMA, depth, confidence, colour codes, contours, the auto range, the centre
+medians and the colour images run after the heads (csrc/live.hip). Camera capture, windows and text overlays stay with
+the host application. Not reproduced: OpenCV's intermediate uint8 rounding and fixed-point interpolation tables, and
+the bytes of its colormap tables.
+"""
+
+from __future__ import annotations
+
+import json
+from dataclasses import dataclass
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+COLORMAP_NAMES = ("turbo", "inferno", "magma", "viridis")
+COLORMAP_FILE = Path(__file__).resolve().parent / "colormaps.json"
+DEPTH_VIS_RANGE_M = (0.0, 10.0)
+DEPTH_CONTOUR_STEP_M = 0.5
+CONFIDENCE_COLORMAP = "viridis"
+CONFIDENCE_VIS_RANGE = (0.0, 5.0)
+MAX_CENTER_WINDOW = 63
+
+
+# ---------------------------------------------------------------------- host helpers (numpy, float64)
+def colormap_lut(name: str) -> np.ndarray:
+    """[256, 3] uint8 BGR table of one of COLORMAP_NAMES (generated from matplotlib's listed colormaps by
+    tools/gen_colormap_luts.py; OpenCV took its tables from the same source, byte equality with cv2 is not pinned)."""
+    if name not in COLORMAP_NAMES:
+        raise ValueError(f"unknown colormap {name!r}: one of {COLORMAP_NAMES}")
+    return load_colormaps()[COLORMAP_NAMES.index(name)]
+
+
+_colormaps = None
+
+
+def load_colormaps() -> np.ndarray:
+    """The committed tables (colormaps.json: {"names": [...], "bgr": [4][256][3]}) as one [4, 256, 3] uint8 array, in
+    the order of COLORMAP_NAMES."""
+    global _colormaps
+    if _colormaps is None:
+        data = json.loads(COLORMAP_FILE.read_text())
+        luts = np.asarray(data["bgr"], dtype=np.uint8)
+        if tuple(data["names"]) != COLORMAP_NAMES or luts.shape != (len(COLORMAP_NAMES), 256, 3):
+            raise ValueError(f"{COLORMAP_FILE}: expected the tables of {COLORMAP_NAMES}, [4][256][3]")
+        _colormaps = luts
+    return _colormaps
+
+
+def rectify_maps(mtx, dist, R, P, image_size) -> tuple[np.ndarray, np.ndarray]:
+    """Undistort-rectify maps in OpenCV's CV_16SC2 fixed-point format for image_size = (width, height):
+    map1 int16 [h, w, 2] (integer x, y) and map2 uint16 [h, w] (fy5 << 5 | fx5, fractions in 1/32 px).
+
+    For every destination pixel (u, v): the ray (P[:, :3] @ R)^-1 [u, v, 1], normalised by its z, distorted with the
+    radial (k1..k6, rational) and tangential (p1, p2) model, projected through `mtx`; the source coordinate is
+    quantised as round_half_even(32 * coord)."""
+    mtx = np.asarray(mtx, dtype=np.float64)
+    R = np.eye(3) if R is None else np.asarray(R, dtype=np.float64)
+    P = np.asarray(P, dtype=np.float64)
+    d = np.zeros(8, dtype=np.float64)
+    dv = np.asarray(dist if dist is not None else [], dtype=np.float64).reshape(-1)[:8]
+    d[:dv.size] = dv
+    k1, k2, p1, p2, k3, k4, k5, k6 = d
+    w, h = int(image_size[0]), int(image_size[1])
+    inv = np.linalg.inv(P[:3, :3] @ R)
+    u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    X = inv[0, 0] * u + inv[0, 1] * v + inv[0, 2]
+    Y = inv[1, 0] * u + inv[1, 1] * v + inv[1, 2]
+    Z = inv[2, 0] * u + inv[2, 1] * v + inv[2, 2]
+    x, y = X / Z, Y / Z
+    r2 = x * x + y * y
+    radial = (1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))) / (1.0 + r2 * (k4 + r2 * (k5 + r2 * k6)))
+    xd = x * radial + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+    yd = y * radial + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+    sx = mtx[0, 0] * xd + mtx[0, 2]
+    sy = mtx[1, 1] * yd + mtx[1, 2]
+    return quantize_maps(sx, sy)
+
+
+def quantize_maps(sx: np.ndarray, sy: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """Float source coordinates -> (map1 int16 [h, w, 2], map2 uint16 [h, w]), round_half_even(32 * coord), the
+    integer part saturated to int16."""
+    qx = np.rint(32.0 * np.asarray(sx, dtype=np.float64)).astype(np.int64)
+    qy = np.rint(32.0 * np.asarray(sy, dtype=np.float64)).astype(np.int64)
+    map1 = np.stack([np.clip(qx >> 5, -32768, 32767), np.clip(qy >> 5, -32768, 32767)], axis=-1).astype(np.int16)
+    map2 = (((qy & 31) << 5) | (qx & 31)).astype(np.uint16)
+    return map1, map2
+
+
+def estimate_baseline_m(P1=None, P2=None, T=None) -> float | None:
+    """Stereo baseline in metres: |P2[0, 3] / P1[0, 0]| when both projections are given and that is finite and
+    positive, else the norm of T (>= 3 values), else None."""
+    if P1 is not None and P2 is not None:
+        f = float(np.asarray(P1)[0, 0])
+        if np.isfinite(f) and abs(f) > 1e-9:
+            b = abs(-float(np.asarray(P2)[0, 3]) / f)
+            if np.isfinite(b) and b > 0.0:
+                return b
+    if T is not None:
+        t = np.asarray(T, dtype=np.float64).reshape(-1)
+        if t.size >= 3:
+            b = float(np.linalg.norm(t))
+            if np.isfinite(b) and b > 0.0:
+                return b
+    return None
+
+
+@dataclass
+class Rectification:
+    """The reference's RectificationData: fixed-point maps of both sides and the rectified geometry."""
+
+    map_l_1: np.ndarray
+    map_l_2: np.ndarray
+    map_r_1: np.ndarray
+    map_r_2: np.ndarray
+    image_size: tuple[int, int]  # (width, height)
+    focal_length_px: float
+    baseline_m: float | None
+
+
+@dataclass
+class Calibration:
+    focal_length_px: float | None
+    baseline_m: float | None
+    calibration_width_px: int | None
+    rectification: Rectification | None
+
+
+def load_calibration(path, rectify: bool = True) -> Calibration:
+    """Read the reference's stereo calibration .npz (keys mtx_l, dist_l, mtx_r, dist_r, R1, R2, P1, P2, image_size,
+    optionally T). The geometry needs only P1 / P2 / T / image_size (mtx_l's focal length when P1 is absent); the
+    rectification maps are built when all of their keys are present and `rectify` is set, and then define the focal
+    length, baseline and calibration width, as in the reference's main()."""
+    with np.load(path) as data:
+        d = {k: data[k] for k in data.files}
+    P1, P2, T = d.get("P1"), d.get("P2"), d.get("T")
+    if P1 is not None:
+        focal = float(P1[0, 0])
+    elif "mtx_l" in d:
+        focal = float(d["mtx_l"][0, 0])
+    else:
+        focal = None
+    if focal is not None and (not np.isfinite(focal) or focal <= 0.0):
+        focal = None
+    baseline = estimate_baseline_m(P1, P2, T)
+    width = int(np.asarray(d["image_size"]).reshape(-1)[0]) if "image_size" in d else None
+    rect = None
+    need = ("mtx_l", "dist_l", "mtx_r", "dist_r", "R1", "R2", "P1", "P2", "image_size")
+    if rectify and all(k in d for k in need):
+        size = tuple(int(v) for v in np.asarray(d["image_size"]).reshape(-1)[:2])
+        ml1, ml2 = rectify_maps(d["mtx_l"], d["dist_l"], d["R1"], P1, size)
+        mr1, mr2 = rectify_maps(d["mtx_r"], d["dist_r"], d["R2"], P2, size)
+        rect = Rectification(ml1, ml2, mr1, mr2, size, float(P1[0, 0]), baseline)
+        focal, width = rect.focal_length_px, size[0]
+    return Calibration(focal, baseline, width, rect)
+
+
+# ---------------------------------------------------------------------- the device path
+class LiveResult:
+    """Device tensors of one step (views of LiveDepth's buffers: the next step overwrites them). depth_m,
+    confidence and confidence_vis are None when depth / uncertainty is off."""
+
+    __slots__ = ("disparity", "logvar", "depth_m", "confidence", "depth_vis", "confidence_vis", "left_view", "_live")
+
+    def __init__(self, live, **kw):
+        self._live = live
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def readout(self) -> tuple[float, float, float]:
+        """(center_disparity, center_depth_m, center_confidence) of the latest step: one 12-byte copy and the only
+        host synchronisation of the frame path."""
+        return self._live._readout()
+
+
+class LiveDepth:
+    def __init__(self, model, model_size=(320, 240), rectification=None, focal_length_px=None, baseline_m=None,
+                 calibration_width_px=None, uncertainty=True, colormap="turbo", ema_alpha=0.0, center_window=15):
+        """model: an eval-mode StereoUNet (in_channels 6) on a HIP device. model_size = (width, height).
+        rectification: an object with the reference's RectificationData attributes (map_l_1, map_l_2, map_r_1,
+        map_r_2, image_size, focal_length_px, baseline_m); when given it defines the geometry (depth_live_dl.py:
+        407-410). Depth is on when a baseline and a focal length scaled to the model width exist (:412-423).
+        colormap: a name of COLORMAP_NAMES or a [256, 3] uint8 BGR table."""
+        if not 0.0 <= float(ema_alpha) <= 1.0:
+            raise ValueError("ema_alpha must be in [0, 1]")
+        if not 0 <= int(center_window) <= MAX_CENTER_WINDOW:
+            raise ValueError(f"center_window must be in [0, {MAX_CENTER_WINDOW}]")
+        if model.in_channels != 6:
+            raise ValueError("LiveDepth needs a stereo model (in_channels 6)")
+        self.model = model
+        self.W, self.H = int(model_size[0]), int(model_size[1])
+        if self.H % 16 or self.W % 16 or self.H <= 0 or self.W <= 0:
+            raise ValueError("model_size must be positive multiples of 16 (four 2x2 pools)")
+        self.rectification = rectification
+        if rectification is not None:
+            focal_length_px = rectification.focal_length_px
+            baseline_m = rectification.baseline_m
+            calibration_width_px = rectification.image_size[0]
+        focal_model = None
+        if focal_length_px is not None and calibration_width_px is not None and calibration_width_px > 0:
+            focal_model = focal_length_px * (self.W / float(calibration_width_px))
+        self.depth_enabled = baseline_m is not None and focal_model is not None
+        self.focal_length_px_model, self.baseline_m = focal_model, baseline_m
+        self.uncertainty = bool(uncertainty)
+        self.ema_alpha = float(ema_alpha)
+        self.center_window = int(center_window)
+        lut = colormap_lut(colormap) if isinstance(colormap, str) else np.asarray(colormap)
+        if lut.shape != (256, 3) or lut.dtype != np.uint8:
+            raise ValueError("colormap: a name or a [256, 3] uint8 BGR table")
+        self._lut_host = (np.ascontiguousarray(lut), colormap_lut(CONFIDENCE_COLORMAP))
+        self._first = True
+        self._buf = None  # device buffers of one (device, capture size)
+        self._key = None
+        self._stage_i = 0
+
+    def reset(self) -> None:
+        """Forget the EMA state: the next frame's prediction is taken as is."""
+        self._first = True
+
+    # ------------------------------------------------------------------ buffers
+    def _alloc(self, device, Hc: int, Wc: int):
+        H, W = self.H, self.W
+        with torch.inference_mode(False):  # written in place by later steps, in or out of inference mode
+            def dev(shape, dtype):
+                return torch.empty(shape, dtype=dtype, device=device)
+
+            b = {
+                "disp": dev((1, 1, H, W), torch.float32), "logvar": dev((1, 1, H, W), torch.float32),
+                "state": dev((H, W), torch.float32), "depth": dev((H, W), torch.float32),
+                "conf": dev((H, W), torch.float32), "dcode": dev((H, W), torch.uint8), "ccode": dev((H, W), torch.uint8),
+                "edge": dev((H, W), torch.uint8), "depth_vis": dev((Hc, Wc, 3), torch.uint8),
+                "conf_vis": dev((Hc, Wc, 3), torch.uint8), "left_view": dev((Hc, Wc, 3), torch.uint8),
+                "view": dev((Hc, Wc, 3), torch.uint8), "center": dev((3,), torch.float32),
+                "sel": torch.zeros(8, dtype=torch.float32, device=device),
+                "sel_ws": torch.zeros(L.call("sd_live_select_ws_bytes") // 4, dtype=torch.int32, device=device),
+                "lut_a": torch.as_tensor(self._lut_host[0]).to(device), "lut_b": torch.as_tensor(self._lut_host[1]).to(device),
+                # numpy frames: a ring of pinned staging pairs (a slot is reused three steps later)
+                "pin": [torch.empty((2, Hc, Wc, 3), dtype=torch.uint8, pin_memory=True) for _ in range(3)],
+                "pin_ev": [None, None, None],
+                "frames": [dev((2, Hc, Wc, 3), torch.uint8) for _ in range(3)],
+                "center_host": torch.full((3,), float("nan"), dtype=torch.float32, pin_memory=True),
+            }
+            r = self.rectification
+            if r is not None:
+                for side in ("l", "r"):
+                    m1 = np.ascontiguousarray(getattr(r, f"map_{side}_1"))
+                    m2 = np.ascontiguousarray(getattr(r, f"map_{side}_2"))
+                    if m1.shape != (Hc, Wc, 2) or m1.dtype != np.int16 or m2.shape != (Hc, Wc) or m2.dtype != np.uint16:
+                        raise ValueError("rectification maps: map1 int16 [Hc, Wc, 2] and map2 uint16 [Hc, Wc] "
+                                         "(cv2.initUndistortRectifyMap(..., cv2.CV_16SC2) or rectify_maps)")
+                    b[f"m1{side}"] = torch.as_tensor(m1).to(device)
+                    b[f"m2{side}"] = torch.as_tensor(m2.view(np.int16)).to(device)
+        self._buf, self._key = b, (device, Hc, Wc)
+        self._first = True
+
+    def _frames(self, frame_l, frame_r, device):
+        """Both frames on the device, uint8 [Hc, Wc, 3]. numpy frames: pinned staging, non_blocking copies."""
+        if isinstance(frame_l, torch.Tensor) != isinstance(frame_r, torch.Tensor):
+            raise TypeError("both frames must be numpy arrays or both device tensors")
+        shape = tuple(frame_l.shape)
+        if len(shape) != 3 or shape[2] != 3 or tuple(frame_r.shape) != shape:
+            raise ValueError(f"frames must be uint8 [Hc, Wc, 3] of one size, got {shape} and {tuple(frame_r.shape)}")
+        r = self.rectification
+        if r is not None and (shape[1], shape[0]) != tuple(r.image_size):
+            raise RuntimeError(f"Capture size mismatch. Expected calibration size={tuple(r.image_size)}, "
+                               f"got={(shape[1], shape[0])}.")
+        if self._key != (device, shape[0], shape[1]):
+            self._alloc(device, shape[0], shape[1])
+        if isinstance(frame_l, torch.Tensor):
+            if frame_l.dtype != torch.uint8 or frame_r.dtype != torch.uint8 or frame_l.device != device \
+                    or frame_r.device != device:
+                raise ValueError("device frames must be uint8 tensors on the model's device")
+            return frame_l.contiguous(), frame_r.contiguous()
+        if frame_l.dtype != np.uint8 or frame_r.dtype != np.uint8:
+            raise ValueError("frames must be uint8")
+        b = self._buf
+        i = self._stage_i
+        self._stage_i = (i + 1) % 3
+        if b["pin_ev"][i] is not None:
+            b["pin_ev"][i].synchronize()  # the upload of three steps ago: long complete unless frames queue up
+        else:
+            b["pin_ev"][i] = torch.cuda.Event()
+        pin = b["pin"][i].numpy()
+        pin[0] = frame_l
+        pin[1] = frame_r
+        b["frames"][i].copy_(b["pin"][i], non_blocking=True)
+        b["pin_ev"][i].record(torch.cuda.current_stream(device))
+        return b["frames"][i][0], b["frames"][i][1]
+
+    # ------------------------------------------------------------------ one frame
+    def step(self, frame_l, frame_r) -> LiveResult:
+        """One frame pair (uint8 BGR [Hc, Wc, 3], numpy or device tensors) through rectification, the model and the
+        display stage. Launches only: no host synchronisation, and no allocation after the first call at a size."""
+        model = self.model
+        if model.training:
+            raise RuntimeError("LiveDepth runs the inference forward: call model.eval()")
+        eng = model.engine()
+        with torch.cuda.device(eng.device):
+            return self._step(eng, frame_l, frame_r)
+
+    def _step(self, eng, frame_l, frame_r) -> LiveResult:
+        H, W = self.H, self.W
+        fl, fr = self._frames(frame_l, frame_r, eng.device)
+        b = self._buf
+        Hc, Wc = self._key[1], self._key[2]
+        maps = [L.ptr(b.get(k)) for k in ("m1l", "m2l", "m1r", "m2r")]
+
+        def pack(xin, amax, slot, clear, stream):
+            L.call("sd_live_frontend", eng.sd_dtype, fl.data_ptr(), fr.data_ptr(), Hc, Wc, *maps, H, W, xin, None, amax,
+                   slot, clear, stream)
+
+        eng.pack_weights(cached=True, train=False)
+        eng.forward_packed(H, W, pack)
+        logvar = b["logvar"] if self.uncertainty else None
+        eng.heads(L.SD_HEADS_INFER, disp=b["disp"], logvar=logvar)
+        s = L.stream_handle(eng.device)
+        view = fl
+        if maps[0] is not None:
+            L.call("sd_live_rectify", fl.data_ptr(), Hc, Wc, maps[0], maps[1], b["view"].data_ptr(), s)
+            view = b["view"]
+        a = self.ema_alpha
+        copy = int(self._first or a <= 0.0)
+        self._first = False
+        on = self.depth_enabled
+        fb = float(np.float32(float(self.focal_length_px_model) * float(self.baseline_m))) if on else 0.0
+        dlo, dhi = DEPTH_VIS_RANGE_M
+        clo, chi = CONFIDENCE_VIS_RANGE
+        L.call("sd_live_post", b["disp"].data_ptr(), L.ptr(logvar), H, W, b["state"].data_ptr(), copy,
+               float(np.float32(a)), float(np.float32(1.0 - a)), int(on), fb, b["depth"].data_ptr() if on else None,
+               b["conf"].data_ptr() if self.uncertainty else None, b["dcode"].data_ptr() if on else None,
+               float(np.float32(dlo)), float(np.float32(max(dhi - dlo, 1e-6))),
+               b["ccode"].data_ptr() if self.uncertainty else None, float(np.float32(clo)),
+               float(np.float32(max(chi - clo, 1e-6))), s)
+        if on:
+            L.call("sd_live_contours", b["depth"].data_ptr(), H, W, float(np.float32(dlo)), float(np.float32(dhi)),
+                   float(np.float32(DEPTH_CONTOUR_STEP_M)), b["edge"].data_ptr(), s)
+        else:  # the disparity in its own 2nd..98th percentile range
+            L.call("sd_live_select", b["state"].data_ptr(), H, W, b["sel_ws"].data_ptr(), b["sel"].data_ptr(),
+                   b["dcode"].data_ptr(), s)
+        L.call("sd_live_center", b["state"].data_ptr(), b["depth"].data_ptr() if on else None,
+               b["conf"].data_ptr() if self.uncertainty else None, H, W, self.center_window, b["center"].data_ptr(), s)
+        unc = self.uncertainty
+        L.call("sd_live_compose", b["dcode"].data_ptr(), b["lut_a"].data_ptr(), b["depth_vis"].data_ptr(),
+               b["ccode"].data_ptr() if unc else None, b["lut_b"].data_ptr() if unc else None,
+               b["conf_vis"].data_ptr() if unc else None, b["edge"].data_ptr() if on else None,
+               view.data_ptr() if on else None, b["left_view"].data_ptr() if on else None, H, W, Hc, Wc, s)
+        return LiveResult(self, disparity=b["state"], logvar=None if logvar is None else logvar[0, 0],
+                          depth_m=b["depth"] if on else None, confidence=b["conf"] if unc else None,
+                          depth_vis=b["depth_vis"], confidence_vis=b["conf_vis"] if unc else None,
+                          left_view=b["left_view"] if on else view)
+
+    def _readout(self) -> tuple[float, float, float]:
+        b = self._buf
+        if b is None:
+            raise RuntimeError("readout() before the first step")
+        b["center_host"].copy_(b["center"], non_blocking=True)
+        torch.cuda.current_stream(self._key[0]).synchronize()
+        c = b["center_host"]
+        return float(c[0]), float(c[1]), float(c[2])

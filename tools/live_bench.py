@@ -1,0 +1,202 @@
+#!/usr/bin/env python3
+"""Time the live loop's frame path on the GPU: ms per frame, by HIP events and by wall clock, after warm-up.
+
+  (i)  device : LiveDepth.step + readout (uint8 frames in, uint8 images and three scalars out)
+  (ii) host   : the same frame served as before the device path existed: the numpy front end of the test oracle
+                (tests/live_ref.py: remap, resize, /255), the fp32 upload from pageable memory,
+                model(x, return_uncertainty=True), two .cpu() copies, the numpy post stage of the oracle.
+                Its stages are also timed one by one (wall clock). The oracle's numpy is float64 and not tuned; an
+                application with cv2 spends less in the two numpy stages, so read them as an upper bound and the
+                upload / forward / read-back lines as they are.
+  stages      : each new C-ABI stage alone, GPU time per call by HIP events over back-to-back launches, next to the
+                forward it wraps (model(x) on a device tensor, events).
+
+    python tools/live_bench.py --frames 640x480 --models 320x240,960x720 --precisions fp8,bf16 --json out.json
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+import live_ref as R  # noqa: E402
+from stereo_depth_estimation_amd import _lib as L  # noqa: E402
+from stereo_depth_estimation_amd import live  # noqa: E402
+from stereo_depth_estimation_amd.model import StereoUNet  # noqa: E402
+
+
+def _size(s: str) -> tuple[int, int]:
+    w, h = s.lower().split("x")
+    return int(w), int(h)
+
+
+def _events(fn, iters: int, warmup: int) -> tuple[float, float]:
+    """(ms per call by HIP events, ms per call by wall clock) of fn(), whose work ends on the current stream."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters, (time.perf_counter() - t0) * 1e3 / iters
+
+
+def _wall(fn, iters: int, warmup: int) -> float:
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / iters
+
+
+def _scene(rng, wc: int, hc: int):
+    """A smooth synthetic stereo pair (uint8 BGR) and mildly distorted rectification maps."""
+    y, x = np.mgrid[0:hc, 0:wc]
+    base = 127 + 80 * np.sin(x / 23.0) * np.cos(y / 17.0)
+    frames = []
+    for shift in (0, 9):
+        img = np.stack([np.roll(base, shift + 3 * c, axis=1) for c in range(3)], axis=-1)
+        frames.append(np.clip(img + rng.normal(0, 6, img.shape), 0, 255).astype(np.uint8))
+    K = np.array([[0.8 * wc, 0, wc / 2.0], [0, 0.8 * wc, hc / 2.0], [0, 0, 1]])
+    P1 = np.hstack([K, np.zeros((3, 1))])
+    P2 = P1.copy()
+    P2[0, 3] = -0.8 * wc * 0.12
+    dist = np.array([-0.12, 0.03, 0.001, -0.001, 0.0])
+    ml = live.rectify_maps(K, dist, np.eye(3), P1, (wc, hc))
+    mr = live.rectify_maps(K, -dist, np.eye(3), P2, (wc, hc))
+    rect = live.Rectification(ml[0], ml[1], mr[0], mr[1], (wc, hc), float(P1[0, 0]), live.estimate_baseline_m(P1, P2))
+    return frames, rect
+
+
+def bench_one(precision: str, wm: int, hm: int, wc: int, hc: int, iters: int, warmup: int, host_iters: int) -> dict:
+    dev = torch.device("cuda")
+    rng = np.random.default_rng(0)
+    (fl, fr), rect = _scene(rng, wc, hc)
+    torch.manual_seed(0)
+    model = StereoUNet(base_channels=32, precision=precision).to(dev).eval()
+    ld = live.LiveDepth(model, (wm, hm), rectification=rect)
+    out = {"precision": precision, "model": f"{wm}x{hm}", "frames": f"{wc}x{hc}"}
+    with torch.inference_mode():
+        # ---- (i) the device path
+        def device_frame():
+            ld.step(fl, fr).readout()
+
+        ev, wall = _events(device_frame, iters, warmup)
+        out["device_ms_events"], out["device_ms_wall"] = ev, wall
+
+        # ---- the forward alone, and each new stage alone (GPU time, events)
+        x = torch.rand(1, 6, hm, wm, device=dev)
+        out["forward_ms_events"] = _events(lambda: model(x, return_uncertainty=True), iters, warmup)[0]
+        b, s = ld._buf, L.stream_handle(dev)
+        eng = model.engine()
+        fld, frd = b["frames"][0][0], b["frames"][0][1]
+        maps = [b[k].data_ptr() for k in ("m1l", "m2l", "m1r", "m2r")]
+        xin = eng.ws.t["xin"].data_ptr()
+        f32 = lambda v: float(np.float32(v))  # noqa: E731
+        fb = f32(ld.focal_length_px_model * ld.baseline_m)
+        stages = {
+            "frontend": lambda: L.call("sd_live_frontend", eng.sd_dtype, fld.data_ptr(), frd.data_ptr(), hc, wc, *maps,
+                                       hm, wm, xin, None, None, 0, -1, s),
+            "rectify_view": lambda: L.call("sd_live_rectify", fld.data_ptr(), hc, wc, maps[0], maps[1],
+                                           b["view"].data_ptr(), s),
+            "post": lambda: L.call("sd_live_post", b["disp"].data_ptr(), b["logvar"].data_ptr(), hm, wm,
+                                   b["state"].data_ptr(), 1, 0.0, 1.0, 1, fb, b["depth"].data_ptr(),
+                                   b["conf"].data_ptr(), b["dcode"].data_ptr(), 0.0, 10.0, b["ccode"].data_ptr(), 0.0,
+                                   5.0, s),
+            "contours": lambda: L.call("sd_live_contours", b["depth"].data_ptr(), hm, wm, 0.0, 10.0, 0.5,
+                                       b["edge"].data_ptr(), s),
+            "select_auto_range": lambda: L.call("sd_live_select", b["state"].data_ptr(), hm, wm,
+                                                b["sel_ws"].data_ptr(), b["sel"].data_ptr(), b["ccode"].data_ptr(), s),
+            "center": lambda: L.call("sd_live_center", b["state"].data_ptr(), b["depth"].data_ptr(),
+                                     b["conf"].data_ptr(), hm, wm, ld.center_window, b["center"].data_ptr(), s),
+            "compose": lambda: L.call("sd_live_compose", b["dcode"].data_ptr(), b["lut_a"].data_ptr(),
+                                      b["depth_vis"].data_ptr(), b["ccode"].data_ptr(), b["lut_b"].data_ptr(),
+                                      b["conf_vis"].data_ptr(), b["edge"].data_ptr(), b["view"].data_ptr(),
+                                      b["left_view"].data_ptr(), hm, wm, hc, wc, s),
+        }
+        out["stage_us"] = {k: 1e3 * _events(fn, 4 * iters, warmup)[0] for k, fn in stages.items()}
+        used = ("frontend", "rectify_view", "post", "contours", "center", "compose")  # the depth-enabled frame
+        out["stages_ms_sum"] = sum(out["stage_us"][k] for k in used) / 1e3
+
+        # ---- (ii) the host path, whole and stage by stage
+        lut_a, lut_b = live.colormap_lut("turbo"), live.colormap_lut("viridis")
+        maps_l, maps_r = (rect.map_l_1, rect.map_l_2), (rect.map_r_1, rect.map_r_2)
+        focal, base = float(ld.focal_length_px_model), float(ld.baseline_m)
+        keep = {}
+
+        def h_front():
+            keep["x"] = torch.from_numpy(R.front_end(fl, fr, maps_l, maps_r, hm, wm).astype(np.float32)).unsqueeze(0)
+            keep["view"] = R.view_u8(fl, *maps_l)
+
+        def h_upload():
+            keep["xd"] = keep["x"].to(dev)
+
+        def h_forward():
+            keep["d"], keep["lv"] = model(keep["xd"], return_uncertainty=True)
+
+        def h_readback():
+            keep["dn"] = keep["d"][0, 0].cpu().numpy().astype(np.float32)
+            keep["ln"] = keep["lv"][0, 0].cpu().numpy().astype(np.float32)
+
+        def h_post():
+            R.host_post(keep["dn"], keep["ln"], keep["view"], lut_a, lut_b, focal, base)
+
+        def host_frame():
+            for f in (h_front, h_upload, h_forward, h_readback, h_post):
+                f()
+
+        out["host_ms_wall"] = _wall(host_frame, host_iters, 2)
+        out["host_stage_ms_wall"] = {f.__name__[2:]: _wall(f, host_iters, 1)
+                                     for f in (h_front, h_upload, h_forward, h_readback, h_post)}
+    return out
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--frames", default="640x480")
+    ap.add_argument("--models", default="320x240,960x720")
+    ap.add_argument("--precisions", default="fp8,bf16")
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--host-iters", type=int, default=5)
+    ap.add_argument("--json", type=Path, default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("live_bench needs a HIP device: there is no CPU fallback and no CPU timing")
+    wc, hc = _size(args.frames)
+    rows = []
+    for precision in args.precisions.split(","):
+        for m in args.models.split(","):
+            wm, hm = _size(m)
+            row = bench_one(precision, wm, hm, wc, hc, args.iters, args.warmup, args.host_iters)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    print("\n| precision | model | device path ms (events / wall) | forward ms | new stages ms | host path ms (wall) |")
+    print("|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['precision']} | {r['model']} | {r['device_ms_events']:.3f} / {r['device_ms_wall']:.3f} | "
+              f"{r['forward_ms_events']:.3f} | {r['stages_ms_sum']:.3f} | {r['host_ms_wall']:.1f} |")
+    if args.json:
+        args.json.parent.mkdir(parents=True, exist_ok=True)
+        args.json.write_text(json.dumps(rows, indent=1))
+
+
+if __name__ == "__main__":
+    main()
