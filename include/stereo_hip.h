@@ -451,6 +451,56 @@ int sd_live_compose(const uint8_t* code_a, const uint8_t* lut_a, uint8_t* vis_a,
                     const uint8_t* lut_b, uint8_t* vis_b, const uint8_t* edge, const uint8_t* view, uint8_t* left_view,
                     int H, int W, int Hc, int Wc, sd_stream s);
 
+/* ---- semi-global matcher of the classical live loop (live_camera/depth_live.py:67-83 build_matcher, :158-178) ----
+ * The algorithm is stated in INTEGRATION.md ("The semi-global matcher"): OpenCV's StereoSGBM step by step with three
+ * paths, integer arithmetic up to the int16 disparity (16 * d, invalid = 16 * (min_disparity - 1)), pinned to the NumPy
+ * restatement in tests/sgm_ref.py bit for bit; equality with cv2's bytes is not claimed. Images are uint8 [H][W], B = 1;
+ * volumes are uint16 [H][W][D], d fastest, defined for x >= min_disparity + D. Parameters: min_disparity >= 0,
+ * D = num_disparities a multiple of 16 in [16, 256], block_size odd in [3, 11], 0 <= P1 <= P2 and
+ * 3 * (block_size^2 * (2 * pre_filter_cap + 63) + P2) <= 65535 (every sum fits uint16), else SD_EINVAL. All buffers
+ * are the caller's, nothing allocates or synchronises (graph-capturable). */
+/* cvtColor(BGR2GRAY) (:158-159): gray = (1868 B + 9617 G + 4899 R + 8192) >> 14 of a BGR uint8 [H][W][3] view. */
+int sd_sgm_gray(const uint8_t* bgr, int H, int W, uint8_t* gray, sd_stream s);
+/* The x-Sobel prefilter inside StereoSGBM.compute (:161): clip(2 (a[y][x+1] - a[y][x-1]) + (a[y-1][x+1] - a[y-1][x-1])
+ * + (a[y+1][x+1] - a[y+1][x-1]), -cap, cap) + cap, edge replicate. */
+int sd_sgm_prefilter(const uint8_t* gray, int H, int W, int cap, uint8_t* out, sd_stream s);
+/* Pixel cost (Birchfield-Tomasi of the prefiltered planes + that of the gray planes >> 2) summed over the
+ * block_size^2 window (x clamped to [maxD, W - 1], y to [0, H - 1]) -> C. tmp: a second volume of C's size (the row
+ * sums of the separable block sum; S serves before the first path writes it). Both 8-B aligned. */
+int sd_sgm_cost(const uint8_t* gray_l, const uint8_t* gray_r, const uint8_t* pre_l, const uint8_t* pre_r, int H, int W,
+                int min_disparity, int num_disparities, int block_size, uint16_t* C, uint16_t* tmp, sd_stream s);
+/* One aggregation path L(p, d) = C + min(L(q, d), L(q, d -+ 1) + P1, min L(q) + P2) - min L(q):
+ * pass 0 top -> down, S = L; pass 1 left -> right, S += L. */
+int sd_sgm_aggregate(const uint16_t* C, int H, int W, int min_disparity, int num_disparities, int P1, int P2, int pass,
+                     uint16_t* S, sd_stream s);
+/* The right -> left path on top of S (passes 0 and 1), then per pixel, x descending: the winner (lowest d of the
+ * minimum), the uniqueness test, the right-view disparity, the sub-pixel value; then the left-right check
+ * (disp12_max_diff < 0: none). q int16 [H][W]; optional S_total (the three-path sum, uint16 volume) and q_raw (the
+ * values before the left-right check). W <= 4096. */
+int sd_sgm_winner(const uint16_t* C, const uint16_t* S, int H, int W, int min_disparity, int num_disparities, int P1,
+                  int P2, int uniqueness_ratio, int disp12_max_diff, uint16_t* S_total, int16_t* q_raw, int16_t* q,
+                  sd_stream s);
+/* Speckle filter in place: connected components (4-neighbour edges between valid pixels that differ by <=
+ * 16 * range) of <= window pixels become invalid_value; window 0: nothing. work: sd_sgm_speckle_ws_bytes(H, W). */
+long long sd_sgm_speckle_ws_bytes(int H, int W);
+int sd_sgm_speckle(int16_t* q, int H, int W, int invalid_value, int window, int range, void* work, sd_stream s);
+/* matcher.compute (:161): prefilter, cost, the three paths, winner, left-right check, speckle filter.
+ * work: sd_sgm_ws_bytes(H, W, D) = 2 * a(2 H W D) + 2 * a(H W) + sd_sgm_speckle_ws_bytes, a = round up to 256;
+ * 256-B aligned. */
+long long sd_sgm_ws_bytes(int H, int W, int D);
+int sd_sgm_compute(const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity, int num_disparities,
+                   int block_size, int P1, int P2, int disp12_max_diff, int uniqueness_ratio, int speckle_window,
+                   int speckle_range, int pre_filter_cap, void* work, int16_t* q, sd_stream s);
+/* The display stage (:161-177): disp = q / 16 as f32, NaN where <= 0; z = row 2 / row 3 of Q (host, 16 doubles, row
+ * major) applied to (x, y, nan_to_num(disp), 1) in fp64, cast to f32, NaN where disp is (reprojectImageTo3D's z);
+ * code = trunc(float32(nan_to_num(disp) * scale + shift)), scale = 255 / (max - min) (0 when equal), shift = -min *
+ * scale in fp64 (cv2.normalize NORM_MINMAX + astype(uint8)); the min / max is found on the device (minmax: 2 words). */
+int sd_sgm_post(const int16_t* q, int H, int W, const double* Q, float* disp, float* z, uint8_t* code,
+                unsigned* minmax, sd_stream s);
+/* np.nanmedian of z's centre window (:168-172; half = max(1, window / 2) around (H/2, W/2), clipped): every non-NaN
+ * value counts (sd_live_center keeps only finite, > 0 values); none: NaN. window <= 63. */
+int sd_sgm_center(const float* z, int H, int W, int window, float* out, sd_stream s);
+
 #ifdef __cplusplus
 }
 #endif

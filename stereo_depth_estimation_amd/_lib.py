@@ -188,6 +188,17 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_live_select": (_i, [_p, _i, _i, _p, _p, _p, _p]),
     "sd_live_center": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
     "sd_live_compose": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "sd_sgm_gray": (_i, [_p, _i, _i, _p, _p]),
+    "sd_sgm_prefilter": (_i, [_p, _i, _i, _i, _p, _p]),
+    "sd_sgm_cost": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "sd_sgm_aggregate": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "sd_sgm_winner": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "sd_sgm_speckle_ws_bytes": (ctypes.c_longlong, [_i, _i]),
+    "sd_sgm_speckle": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
+    "sd_sgm_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
+    "sd_sgm_compute": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "sd_sgm_post": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "sd_sgm_center": (_i, [_p, _i, _i, _i, _p, _p]),
 }
 
 _lib = None

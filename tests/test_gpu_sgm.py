@@ -1,0 +1,311 @@
+"""The semi-global matcher on the device (csrc/sgm.hip, sgm.py; needs an MI355X), B = 1 throughout.
+
+Every stage boundary is array_equal to the NumPy restatement tests/sgm_ref.py: gray, prefilter, the cost volume C, the
+three-path sum S, the disparity before and after the left-right check, after the speckle filter, and the final int16 map
+of sd_sgm_compute. Everything up to there is integer arithmetic, so there is no tolerance. The post stage's disp / z
+are bit-equal too (z is fp64 arithmetic cast once), the display codes equal, the centre distance bit-equal to
+np.nanmedian. The volumes are allocated zeroed and compared whole: nothing may be written for x < maxD.
+"""
+
+import numpy as np
+import pytest
+import torch
+
+import live_ref
+import sgm_ref as R
+from stereo_depth_estimation_amd import _lib as L
+from stereo_depth_estimation_amd import live, sgm
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+# (H, W, D, minD, bs): partial wave; D no power of two, minD > 0, odd W tail; two values per lane (the app's settings);
+# the maximum D and bs (uint16 head-room); W < maxD (all invalid, nothing indexed out of range)
+CASES = [(9, 40, 16, 0, 3), (17, 150, 48, 3, 5), (33, 200, 128, 0, 7), (12, 300, 256, 0, 11), (8, 20, 32, 0, 7)]
+APP_CASE = CASES[2]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+
+
+def _dev(a):
+    a = np.array(a, order="C")  # a writable copy (the shared references are read-only)
+    if a.dtype == np.uint16:
+        a = a.view(np.int16)
+    return torch.as_tensor(a).to(DEV)
+
+
+def _np(t, dtype=None):
+    a = t.cpu().numpy()
+    return a.view(dtype) if dtype is not None else a
+
+
+def _s():
+    return L.stream_handle()
+
+
+def _params(case):
+    H, W, D, minD, bs = case
+    # the app's speckle window on the app's case; a smaller one elsewhere so that components survive on small maps
+    return R.Params(min_disparity=minD, num_disparities=D, block_size=bs,
+                    speckle_window_size=100 if case == APP_CASE else 12)
+
+
+def _scene(case, kind):
+    H, W, D, minD, bs = case
+    rng = np.random.default_rng(1000 * H + W + (7 if kind == "noise" else 0))
+    if kind == "noise":
+        return R.shifted_bgr_scene(rng, H, W, W)  # d0 = W: two independent textures
+    return R.shifted_bgr_scene(rng, H, W, minD + D // 3, noise=12)
+
+
+_refs = {}
+
+
+def _ref(case, kind):
+    """The restatement's stages of one case, computed once and shared (read-only)."""
+    if (case, kind) not in _refs:
+        left, right = _scene(case, kind)
+        p = _params(case)
+        gl, gr = R.gray(left), R.gray(right)
+        st = R.compute_stages(gl, gr, p)
+        st.update(left=left, right=right, gray_l=gl, gray_r=gr)
+        for v in st.values():
+            v.setflags(write=False)
+        _refs[(case, kind)] = st
+    return _refs[(case, kind)]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _assert_bit_equal(got, want):
+    got, want = np.asarray(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan)
+    assert np.array_equal(_bits(got)[~nan], _bits(want)[~nan])
+
+
+# ---------------------------------------------------------------------- the matcher, stage by stage
+@pytest.mark.parametrize("kind", ["shift", "noise"])
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c)))
+def test_every_stage_equals_the_restatement(case, kind):
+    H, W, D, minD, bs = case
+    p = _params(case)
+    ref = _ref(case, kind)
+    s = _s()
+    # stage 1
+    gray = []
+    for side in ("left", "right"):
+        g = torch.empty((H, W), dtype=torch.uint8, device=DEV)
+        frame = _dev(ref[side])
+        L.call("sd_sgm_gray", frame.data_ptr(), H, W, g.data_ptr(), s)
+        gray.append(g)
+    assert np.array_equal(_np(gray[0]), ref["gray_l"]) and np.array_equal(_np(gray[1]), ref["gray_r"])
+    # stage 2
+    pre = []
+    for g in gray:
+        o = torch.empty((H, W), dtype=torch.uint8, device=DEV)
+        L.call("sd_sgm_prefilter", g.data_ptr(), H, W, p.cap, o.data_ptr(), s)
+        pre.append(o)
+    assert np.array_equal(_np(pre[0]), ref["pre_l"]) and np.array_equal(_np(pre[1]), ref["pre_r"])
+    # stages 3, 4
+    C = torch.zeros((H, W, D), dtype=torch.int16, device=DEV)
+    tmp = torch.empty((H, W, D), dtype=torch.int16, device=DEV)
+    L.call("sd_sgm_cost", gray[0].data_ptr(), gray[1].data_ptr(), pre[0].data_ptr(), pre[1].data_ptr(), H, W, minD, D,
+           bs, C.data_ptr(), tmp.data_ptr(), s)
+    assert np.array_equal(_np(C, np.uint16), ref["C"])
+    # stage 5 (two passes into S, the third inside the winner kernel) and stages 6, 7
+    S = torch.zeros((H, W, D), dtype=torch.int16, device=DEV)
+    S_total = torch.zeros((H, W, D), dtype=torch.int16, device=DEV)
+    q_raw = torch.empty((H, W), dtype=torch.int16, device=DEV)
+    q = torch.empty((H, W), dtype=torch.int16, device=DEV)
+    L.call("sd_sgm_aggregate", C.data_ptr(), H, W, minD, D, p.P1, p.P2, 0, S.data_ptr(), s)
+    L.call("sd_sgm_aggregate", C.data_ptr(), H, W, minD, D, p.P1, p.P2, 1, S.data_ptr(), s)
+    L.call("sd_sgm_winner", C.data_ptr(), S.data_ptr(), H, W, minD, D, p.P1, p.P2, p.uniq, p.max_diff,
+           S_total.data_ptr(), q_raw.data_ptr(), q.data_ptr(), s)
+    assert np.array_equal(_np(S_total, np.uint16), ref["S"])
+    assert np.array_equal(_np(q_raw), ref["q_raw"])
+    assert np.array_equal(_np(q), ref["q_lr"])
+    if W > p.maxD and kind == "shift":  # the scene is not degenerate: most of the band right of maxD is matched
+        assert (ref["q_lr"][:, p.maxD:] != p.invalid).mean() > 0.5
+    # stage 8
+    work = torch.empty(L.call("sd_sgm_speckle_ws_bytes", H, W), dtype=torch.uint8, device=DEV)
+    L.call("sd_sgm_speckle", q.data_ptr(), H, W, p.invalid, p.speckle_window, p.speckle_range, work.data_ptr(), s)
+    assert np.array_equal(_np(q), ref["q"])
+    # the whole matcher in one call, and through the Python surface
+    ws = torch.empty(L.call("sd_sgm_ws_bytes", H, W, D), dtype=torch.uint8, device=DEV)
+    out = torch.empty((H, W), dtype=torch.int16, device=DEV)
+    L.call("sd_sgm_compute", gray[0].data_ptr(), gray[1].data_ptr(), H, W, minD, D, bs, p.P1, p.P2, p.max_diff, p.uniq,
+           p.speckle_window, p.speckle_range, p.cap, ws.data_ptr(), out.data_ptr(), s)
+    assert np.array_equal(_np(out), ref["q"])
+    m = sgm.StereoSGM(min_disparity=minD, num_disparities=D, block_size=bs, speckle_window_size=p.speckle_window)
+    got = m.compute(gray[0], gray[1])
+    assert got.dtype == torch.int16 and np.array_equal(_np(got), ref["q"])
+
+
+def test_the_band_left_of_max_disparity_is_invalid():
+    case = (8, 20, 32, 0, 7)  # W < maxD
+    assert (_ref(case, "shift")["q"] == -16).all()
+    ref = _ref(APP_CASE, "shift")
+    assert (ref["q"][:, :128] == -16).all() and (ref["q"][:, 128:] != -16).any()
+
+
+# ---------------------------------------------------------------------- the speckle filter alone
+def _speckle(q, invalid, window, rng_range):
+    H, W = q.shape
+    t = _dev(q)
+    work = torch.empty(L.call("sd_sgm_speckle_ws_bytes", H, W), dtype=torch.uint8, device=DEV)
+    L.call("sd_sgm_speckle", t.data_ptr(), H, W, invalid, window, rng_range, work.data_ptr(), _s())
+    return _np(t)
+
+
+@pytest.mark.parametrize("H,W,window", [(31, 45, 30), (70, 130, 100)])
+def test_speckle_filter_on_crafted_maps(H, W, window):
+    q = R.crafted_speckle_map(H, W, -16, window, 2)
+    want = R.speckle(q, -16, window, 2)
+    # what the crafted map is for (the flood fill's verdicts are asserted in test_sgm_cpu.py)
+    assert (want[q == 160] == 160).all() and (want[q == 400] == -16).all() and (want[q == 800] == 800).all()
+    assert (want[q == 1000] == 1000).all() and (want[q == 2000] == -16).all() and (want[q == 3000] == -16).all()
+    assert np.array_equal(_speckle(q, -16, window, 2), want)
+    assert np.array_equal(_speckle(q, -16, 0, 2), q)  # window 0: the stage is skipped
+
+
+@pytest.mark.parametrize("H,W,window", [(31, 45, 30), (70, 130, 100)])
+def test_speckle_filter_on_random_maps(H, W, window):
+    rng = np.random.default_rng(H)
+    # few levels around the joining threshold (32, 33 apart) and holes: components of every size and shape
+    levels = np.array([100, 132, 165, 197, 230], dtype=np.int16)
+    for hole in (0.35, 0.1):
+        q = levels[rng.integers(0, 2 if hole < 0.2 else 5, (H, W))]
+        q[rng.random((H, W)) < hole] = 48  # the invalid value of min_disparity 4
+        assert np.array_equal(_speckle(q, 48, window, 2), R.speckle(q, 48, window, 2))
+
+
+# ---------------------------------------------------------------------- post stage
+@pytest.fixture(scope="module")
+def calib_Q(golden_dir):
+    with np.load(golden_dir / "sgm_calib.npz") as d:
+        return np.array(d["Q"], dtype=np.float64)
+
+
+def _post(q, Q, window):
+    H, W = q.shape
+    disp = torch.empty((H, W), dtype=torch.float32, device=DEV)
+    z = torch.empty((H, W), dtype=torch.float32, device=DEV)
+    code = torch.empty((H, W), dtype=torch.uint8, device=DEV)
+    mm = torch.zeros(2, dtype=torch.int32, device=DEV)
+    c = torch.empty(1, dtype=torch.float32, device=DEV)
+    Qc = np.ascontiguousarray(Q, dtype=np.float64)
+    qd = _dev(q)
+    L.call("sd_sgm_post", qd.data_ptr(), H, W, Qc.ctypes.data, disp.data_ptr(), z.data_ptr(), code.data_ptr(),
+           mm.data_ptr(), _s())
+    L.call("sd_sgm_center", z.data_ptr(), H, W, window, c.data_ptr(), _s())
+    return _np(disp), _np(z), _np(code), _np(c)[0]
+
+
+@pytest.mark.parametrize("which", ["matched", "random", "flat", "empty"])
+def test_post_stage_is_bit_equal(calib_Q, which):
+    rng = np.random.default_rng(5)
+    if which == "matched":
+        q = _ref(APP_CASE, "shift")["q_lr"]
+    elif which == "random":  # odd sizes, values on both sides of zero, holes in the centre window
+        q = rng.integers(-40, 2000, (31, 45)).astype(np.int16)
+        q[rng.random(q.shape) < 0.3] = -16
+    elif which == "flat":    # max == min: scale 0
+        q = np.full((9, 40), 320, dtype=np.int16)
+    else:                    # nothing valid: the centre distance is NaN
+        q = np.full((9, 40), -16, dtype=np.int16)
+    Q = calib_Q.copy()
+    if which == "random":
+        Q[3, 0], Q[3, 1], Q[2, 0], Q[3, 3] = 0.013, -0.007, 0.21, 0.5  # every term of both rows in play
+    for window in (15, 4):
+        disp, z, code, c = _post(q, Q, window)
+        want_disp, want_z, want_code = R.post(q, Q)
+        _assert_bit_equal(disp, want_disp)
+        _assert_bit_equal(z, want_z)
+        assert np.array_equal(code, want_code)
+        _assert_bit_equal([c], [R.center_distance(want_z, window)])
+    if which in ("matched", "random"):  # the inputs are not degenerate
+        assert code.max() >= 254 and np.isfinite(want_z).any()
+    if which == "random":
+        assert np.isfinite(c)
+
+
+# ---------------------------------------------------------------------- the whole loop body
+def _stagewise(classic, fl, fr, maps):
+    """ClassicDepth.step's outputs from separate entry-point calls on fresh buffers."""
+    H, W = fl.shape[:2]
+    s = _s()
+    rect = []
+    for f, m in ((fl, maps[0]), (fr, maps[1])):
+        t = _dev(f)
+        if m is not None:
+            o, m1, m2 = torch.empty_like(t), _dev(m[0]), _dev(m[1])
+            L.call("sd_live_rectify", t.data_ptr(), H, W, m1.data_ptr(), m2.data_ptr(), o.data_ptr(), s)
+            torch.cuda.synchronize()  # the maps stay alive until the kernel has run
+            t = o
+        rect.append(t)
+    gray = []
+    for t in rect:
+        g = torch.empty((H, W), dtype=torch.uint8, device=DEV)
+        L.call("sd_sgm_gray", t.data_ptr(), H, W, g.data_ptr(), s)
+        gray.append(g)
+    q = classic.matcher.__class__(**MATCHER_KW).compute(gray[0], gray[1])
+    disp, z, code, c = _post(_np(q), classic.Q, classic.center_window)
+    vis = live.colormap_lut("turbo")[code]
+    return rect, q, disp, z, vis, c
+
+
+MATCHER_KW = dict(num_disparities=16, block_size=5, speckle_window_size=10)
+
+
+@pytest.mark.parametrize("with_maps", [False, True])
+def test_classic_depth_step(calib_Q, with_maps):
+    H, W = 48, 64
+    rng = np.random.default_rng(11 + with_maps)
+    fl, fr = R.shifted_bgr_scene(rng, H, W, 5, noise=6)
+    maps = (None, None)
+    rect = None
+    if with_maps:
+        maps = (live_ref.random_maps(rng, H, W, outside=0.0), live_ref.random_maps(rng, H, W, outside=0.0))
+        rect = live.Rectification(maps[0][0], maps[0][1], maps[1][0], maps[1][1], (W, H), 500.0, 0.07)
+    classic = sgm.ClassicDepth(rectification=rect, Q=calib_Q, center_window=15, **MATCHER_KW)
+
+    def check(res, a, b):
+        want_rect, q, disp, z, vis, c = _stagewise(classic, a, b, maps)
+        assert torch.equal(res.rect_left, want_rect[0]) and torch.equal(res.rect_right, want_rect[1])
+        assert res.disparity_q4.dtype == torch.int16 and torch.equal(res.disparity_q4, q)
+        _assert_bit_equal(_np(res.disparity), disp)
+        _assert_bit_equal(_np(res.depth_m), z)
+        assert np.array_equal(_np(res.disp_vis), vis)
+        _assert_bit_equal([res.readout()], [c])
+        return _np(q)
+
+    q = check(classic.step(fl, fr), fl, fr)  # numpy frames
+    if not with_maps:  # the scene is matched, and equals the restatement end to end
+        assert np.array_equal(q, R.compute(R.gray(fl), R.gray(fr), R.Params(**MATCHER_KW)))
+        assert (q[:, 16:] != -16).mean() > 0.5
+    # device frames; a second step at the size allocates nothing
+    dl, dr = _dev(fl), _dev(fr)
+    check(classic.step(dl, dr), fl, fr)
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated()
+    res = classic.step(dl, dr)
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() == before
+    # the step's launches capture into a graph; a replay on new frames gives the eager bytes
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        res = classic.step(dl, dr)
+    fl2, fr2 = R.shifted_bgr_scene(rng, H, W, 9, noise=6)
+    dl.copy_(_dev(fl2))
+    dr.copy_(_dev(fr2))
+    g.replay()
+    torch.cuda.synchronize()
+    q2 = check(res, fl2, fr2)
+    assert not np.array_equal(q, q2)

@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""Time the classical live loop's frame path on the GPU (ClassicDepth: rectify, gray, the semi-global matcher,
+reprojection, centre distance, colour image): ms per frame by HIP events and by wall clock, after warm-up, and each
+C-ABI stage alone, GPU time per call by HIP events over back-to-back launches (as tools/live_bench.py does).
+
+The matcher's reference points are arithmetic, not measurements: the two uint16 volumes C and S are each
+2 * H * W * D bytes. The three recurrences move seven of them (top-down reads C, writes S; left-right reads C and S,
+writes S; right-left reads C and S), and each is one sequential chain of H or W - maxD steps per scan line; the cost
+stage writes its row sums into S as scratch, reads them about twice and writes C. The table prints the volume bytes
+over each stage's time next to the chain's time per step.
+
+    python tools/sgm_bench.py --frames 640x480 --num-disparities 128 --block-size 7 --json out.json
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+from stereo_depth_estimation_amd import _lib as L  # noqa: E402
+from stereo_depth_estimation_amd import live, sgm  # noqa: E402
+
+
+def _events(fn, iters: int, warmup: int) -> tuple[float, float]:
+    """(ms per call by HIP events, ms per call by wall clock) of fn(), whose work ends on the current stream."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters, (time.perf_counter() - t0) * 1e3 / iters
+
+
+def clock_probe(dev, iters: int = 20000) -> float:
+    """Median effective shader clock in MHz under sd_clock_probe's MFMA load (as bench.py reports it)."""
+    n = 256
+    out = torch.zeros(4 * n, dtype=torch.int64, device=dev)
+    sink = torch.zeros(256, dtype=torch.float32, device=dev)
+    L.call("sd_clock_probe", n, iters, out.data_ptr(), sink.data_ptr(), L.stream_handle(dev))
+    torch.cuda.synchronize(dev)
+    o = out.view(n, 4).cpu().double()
+    mhz = ((o[:, 1] - o[:, 0]) / (o[:, 3] - o[:, 2]) * 100.0).sort().values
+    return round(float(mhz[n // 2]), 1)
+
+
+def _scene(rng, wc: int, hc: int):
+    """A textured synthetic stereo pair (uint8 BGR) with a disparity ramp, mildly distorted rectification maps and Q."""
+    base = rng.integers(0, 256, (hc, wc + 128, 3)).astype(np.float64)
+    for _ in range(2):  # a little smoothing: texture with structure at the block size
+        base = (base + np.roll(base, 1, axis=1) + np.roll(base, 1, axis=0)) / 3.0
+    base = (base - base.min()) / (base.max() - base.min()) * 255.0
+    left = base[:, 64:64 + wc]
+    right = np.empty_like(left)
+    for y in range(hc):  # right[x] = left[x + d], d from 8 at the top to 48 at the bottom
+        d = 8 + (40 * y) // hc
+        right[y] = base[y, 64 + d:64 + d + wc]
+    frames = [np.clip(f + rng.normal(0, 3, f.shape), 0, 255).astype(np.uint8) for f in (left, right)]
+    K = np.array([[0.8 * wc, 0, wc / 2.0], [0, 0.8 * wc, hc / 2.0], [0, 0, 1]])
+    P1 = np.hstack([K, np.zeros((3, 1))])
+    P2 = P1.copy()
+    P2[0, 3] = -0.8 * wc * 0.12
+    dist = np.array([-0.05, 0.01, 0.0005, -0.0005, 0.0])
+    ml = live.rectify_maps(K, dist, np.eye(3), P1, (wc, hc))
+    mr = live.rectify_maps(K, -dist, np.eye(3), P2, (wc, hc))
+    rect = live.Rectification(ml[0], ml[1], mr[0], mr[1], (wc, hc), float(P1[0, 0]), 0.12)
+    Q = np.array([[1, 0, 0, -wc / 2.0], [0, 1, 0, -hc / 2.0], [0, 0, 0, 0.8 * wc], [0, 0, 1 / 0.12, 0]])
+    return frames, rect, Q
+
+
+def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int) -> dict:
+    dev = torch.device("cuda", torch.cuda.current_device())
+    (fl, fr), rect, Q = _scene(np.random.default_rng(0), wc, hc)
+    cd = sgm.ClassicDepth(rectification=rect, Q=Q, num_disparities=D, block_size=bs, device=dev)
+    out = {"frames": f"{wc}x{hc}", "num_disparities": D, "block_size": bs, "iters": iters, "warmup": warmup,
+           "clock_mhz_before": clock_probe(dev)}
+
+    def frame():
+        cd.step(fl, fr).readout()
+
+    out["frame_ms_events"], out["frame_ms_wall"] = _events(frame, iters, warmup)
+    res = cd.step(fl, fr)
+    torch.cuda.synchronize()
+    q = res.disparity_q4
+    out["valid_fraction"] = float((q[:, D:] != cd.matcher.invalid_value).float().mean())
+
+    # each stage alone, back-to-back launches on the frame's own buffers
+    b, m, s = cd._buf, cd.matcher, L.stream_handle(dev)
+    H, W, P = hc, wc, hc * wc
+    vol = (2 * P * D + 255) // 256 * 256
+    ws = m.workspace(dev, H, W)
+    C, S = ws.data_ptr(), ws.data_ptr() + vol
+    pl = ws.data_ptr() + 2 * vol
+    pr = pl + (P + 255) // 256 * 256
+    sw = pr + (P + 255) // 256 * 256
+    fld, frd = b["frames"][0][0], b["frames"][0][1]
+    gl, gr = b["gray"][0], b["gray"][1]
+    q_tmp = torch.empty_like(q)
+    agg = (C, H, W, m.min_disparity, D, m.P1, m.P2)
+    stages = {
+        "rectify (x2)": lambda: [L.call("sd_live_rectify", f.data_ptr(), H, W, b[f"m1{k}"].data_ptr(),
+                                        b[f"m2{k}"].data_ptr(), b["rect"][i].data_ptr(), s)
+                                 for i, (f, k) in enumerate(((fld, "l"), (frd, "r")))],
+        "gray (x2)": lambda: [L.call("sd_sgm_gray", b["rect"][i].data_ptr(), H, W, b["gray"][i].data_ptr(), s)
+                              for i in range(2)],
+        "prefilter (x2)": lambda: [L.call("sd_sgm_prefilter", g.data_ptr(), H, W, m.pre_filter_cap, p, s)
+                                   for g, p in ((gl, pl), (gr, pr))],
+        "cost": lambda: L.call("sd_sgm_cost", gl.data_ptr(), gr.data_ptr(), pl, pr, H, W, m.min_disparity, D, bs, C, S, s),
+        "aggregate top-down": lambda: L.call("sd_sgm_aggregate", *agg, 0, S, s),
+        "aggregate right-left + winner": lambda: L.call("sd_sgm_winner", C, S, H, W, m.min_disparity, D, m.P1, m.P2,
+                                                        m.uniqueness_ratio, m.disp12_max_diff, None, None,
+                                                        q_tmp.data_ptr(), s),
+        "aggregate left-right": lambda: L.call("sd_sgm_aggregate", *agg, 1, S, s),
+        "speckle": lambda: (q_tmp.copy_(q), L.call("sd_sgm_speckle", q_tmp.data_ptr(), H, W, m.invalid_value,
+                                                   m.speckle_window_size, m.speckle_range, sw, s)),
+        "post": lambda: L.call("sd_sgm_post", q.data_ptr(), H, W, cd.Q.ctypes.data, b["disp"].data_ptr(),
+                               b["z"].data_ptr(), b["code"].data_ptr(), b["minmax"].data_ptr(), s),
+        "center": lambda: L.call("sd_sgm_center", b["z"].data_ptr(), H, W, cd.center_window, b["center"].data_ptr(), s),
+        "compose": lambda: L.call("sd_live_compose", b["code"].data_ptr(), b["lut"].data_ptr(), b["vis"].data_ptr(),
+                                  None, None, None, None, None, None, H, W, H, W, s),
+    }
+    # the left-right pass adds into S on every launch, so it is timed after the winner kernel (which reads S)
+    out["stage_us"] = {k: 1e3 * _events(fn, iters, warmup)[0] for k, fn in stages.items()}
+    out["stages_ms_sum"] = sum(out["stage_us"].values()) / 1e3
+    volume_bytes = 2 * P * D
+    passes = {"cost": 1, "aggregate top-down": 2, "aggregate left-right": 3, "aggregate right-left + winner": 2}
+    out["volume_bytes"] = volume_bytes
+    out["volume_GBps"] = {k: n * volume_bytes / (out["stage_us"][k] * 1e-6) / 1e9 for k, n in passes.items()}
+    maxD = m.min_disparity + D
+    steps = {"aggregate top-down": H, "aggregate left-right": W - maxD, "aggregate right-left + winner": W - maxD}
+    out["chain_ns_per_step"] = {k: out["stage_us"][k] * 1e3 / n for k, n in steps.items()}
+    agg_us = sum(out["stage_us"][k] for k in steps)
+    out["aggregate_ms"] = agg_us / 1e3
+    out["aggregate_volume_GBps"] = 7 * volume_bytes / (agg_us * 1e-6) / 1e9
+    out["clock_mhz_after"] = clock_probe(dev)
+    return out
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--frames", default="640x480")
+    ap.add_argument("--num-disparities", type=int, default=128)
+    ap.add_argument("--block-size", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--json", type=Path, default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("sgm_bench needs a HIP device: there is no CPU fallback and no CPU timing")
+    w, h = (int(v) for v in args.frames.lower().split("x"))
+    r = bench(w, h, args.num_disparities, args.block_size, args.iters, args.warmup)
+    print(json.dumps(r), flush=True)
+    print(f"\nframe {r['frames']}, D = {r['num_disparities']}, bs = {r['block_size']}: "
+          f"{r['frame_ms_events']:.3f} ms (events) / {r['frame_ms_wall']:.3f} ms (wall) per step + readout; "
+          f"clock {r['clock_mhz_before']} / {r['clock_mhz_after']} MHz; valid {r['valid_fraction']:.2f}")
+    print("\n| stage | us | volume GB/s | ns per chain step |\n|---|---|---|---|")
+    for k, us in r["stage_us"].items():
+        gb = r["volume_GBps"].get(k)
+        ns = r["chain_ns_per_step"].get(k)
+        print(f"| {k} | {us:.1f} | {'' if gb is None else f'{gb:.0f}'} | {'' if ns is None else f'{ns:.0f}'} |")
+    print(f"| sum | {1e3 * r['stages_ms_sum']:.1f} | | |")
+    if args.json:
+        args.json.parent.mkdir(parents=True, exist_ok=True)
+        args.json.write_text(json.dumps(r, indent=1))
+
+
+if __name__ == "__main__":
+    main()
