@@ -457,7 +457,8 @@ int sd_live_compose(const uint8_t* code_a, const uint8_t* lut_a, uint8_t* vis_a,
  * restatement in tests/sgm_ref.py bit for bit; equality with cv2's bytes is not claimed. Images are uint8 [H][W], B = 1;
  * volumes are uint16 [H][W][D], d fastest, defined for x >= min_disparity + D. Parameters: min_disparity >= 0,
  * D = num_disparities a multiple of 16 in [16, 256], block_size odd in [3, 11], 0 <= P1 <= P2 and
- * 3 * (block_size^2 * (2 * pre_filter_cap + 63) + P2) <= 65535 (every sum fits uint16), else SD_EINVAL. All buffers
+ * 3 * (block_size^2 * (2 * pre_filter_cap + 63) + P2) <= 65535 (every sum fits uint16; the modes with more paths put
+ * their path count in place of the 3: sd_sgm_compute_mode), else SD_EINVAL. All buffers
  * are the caller's, nothing allocates or synchronises (graph-capturable). */
 /* cvtColor(BGR2GRAY) (:158-159): gray = (1868 B + 9617 G + 4899 R + 8192) >> 14 of a BGR uint8 [H][W][3] view. */
 int sd_sgm_gray(const uint8_t* bgr, int H, int W, uint8_t* gray, sd_stream s);
@@ -491,6 +492,25 @@ long long sd_sgm_ws_bytes(int H, int W, int D);
 int sd_sgm_compute(const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity, int num_disparities,
                    int block_size, int P1, int P2, int disp12_max_diff, int uniqueness_ratio, int speckle_window,
                    int speckle_range, int pre_filter_cap, void* work, int16_t* q, sd_stream s);
+/* The aggregation modes (cv2.StereoSGBM's constants) and their paths (dy, dx), the predecessor of (y, x) being
+ * (y - dy, x - dx) and a path starting where that lies outside [0, H) x [maxD, W):
+ *   SD_SGM_MODE_3WAY (1,0) (0,1) (0,-1); _HH4 adds (-1,0); _SGBM adds (1,1) (1,-1); _HH is all eight.
+ * The uint16 bound is npaths * (block_size^2 * (2 * pre_filter_cap + 63) + P2) <= 65535 with 3 / 4 / 5 / 8 paths. */
+#define SD_SGM_MODE_SGBM 0
+#define SD_SGM_MODE_HH 1
+#define SD_SGM_MODE_3WAY 2
+#define SD_SGM_MODE_HH4 3
+/* One aggregation path along (dy, dx): dy = +-1 with dx in {-1, 0, 1}, or (0, 1). accumulate 0: S = L, 1: S += L.
+ * Nothing is written for x < maxD; W <= maxD is a successful no-op. (0, -1) is refused: that path runs inside
+ * sd_sgm_winner, on top of the S of all the others. */
+int sd_sgm_aggregate_dir(const uint16_t* C, int H, int W, int min_disparity, int num_disparities, int P1, int P2, int dy,
+                         int dx, int accumulate, uint16_t* S, sd_stream s);
+/* sd_sgm_compute with the paths of `mode`; SD_SGM_MODE_3WAY issues exactly sd_sgm_compute's launches. The further
+ * paths are successive launches that add into S, so the workspace is sd_sgm_ws_bytes for every mode. */
+int sd_sgm_compute_mode(const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
+                        int num_disparities, int block_size, int P1, int P2, int disp12_max_diff, int uniqueness_ratio,
+                        int speckle_window, int speckle_range, int pre_filter_cap, int mode, void* work, int16_t* q,
+                        sd_stream s);
 /* The display stage (:161-177): disp = q / 16 as f32, NaN where <= 0; z = row 2 / row 3 of Q (host, 16 doubles, row
  * major) applied to (x, y, nan_to_num(disp), 1) in fp64, cast to f32, NaN where disp is (reprojectImageTo3D's z);
  * code = trunc(float32(nan_to_num(disp) * scale + shift)), scale = 255 / (max - min) (0 when equal), shift = -min *

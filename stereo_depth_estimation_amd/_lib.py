@@ -22,6 +22,7 @@ SD_IDENT, SD_BNRELU, SD_AFFINE = 0, 1, 2
 SD_EPI_STORE, SD_EPI_STATS, SD_EPI_SPLIT, SD_EPI_PIXSHUF, SD_EPI_SPLIT_STATS = 0, 1, 2, 3, 4
 SD_W_CONV3, SD_W_CONVT, SD_W_ROWSUM = 0, 1, 2
 SD_HEADS_INFER, SD_HEADS_LOSS, SD_HEADS_GRADS = 0, 1, 2
+SD_SGM_MODE_SGBM, SD_SGM_MODE_HH, SD_SGM_MODE_3WAY, SD_SGM_MODE_HH4 = 0, 1, 2, 3  # cv2.StereoSGBM's constants
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -197,6 +198,8 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_sgm_speckle": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     "sd_sgm_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
     "sd_sgm_compute": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "sd_sgm_aggregate_dir": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "sd_sgm_compute_mode": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sd_sgm_post": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "sd_sgm_center": (_i, [_p, _i, _i, _i, _p, _p]),
 }

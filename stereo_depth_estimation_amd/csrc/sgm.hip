@@ -7,7 +7,9 @@
 //                      C[y][x][d] (d fastest)
 //   aggregate        : three scan-line recurrences with d across the 64 lanes of a wave (d = lane + 64 k, k < D / 64
 //                      rounded up): top->down writes S, left->right adds to S, right->left keeps its L in registers,
-//                      forms the total and does the winner, the right-view disparity and the left-right check in flight
+//                      forms the total and does the winner, the right-view disparity and the left-right check in flight.
+//                      The 4-, 5- and 8-path modes add bottom->up and the diagonals between the first two, one launch
+//                      of k_sgm_walk each (S += L); tests/sgm_modes_ref.py restates them
 //   speckle          : union-find over the 4-neighbour graph (atomicMin on parent links), count at the roots, invalidate
 //   post             : disparity, fp64 reprojection, min/max on the device, display codes; the centre nanmedian
 // No allocation, no synchronisation: every entry point is graph-capturable. Workspace is the caller's.
@@ -35,14 +37,29 @@ bool sgm_dims_ok(int H, int W) { return H > 0 && W > 0 && (long long)H * W <= IN
 
 struct SgmParams {
     int minD, D, bs, P1, P2, max_diff, uniq, speckle_window, speckle_range, cap;
+    int npaths = 3;  // paths summed into S: 3 (3-way), 4 (hh4), 5 (sgbm), 8 (hh)
 };
+// the paths of a mode (SD_SGM_MODE_*, cv2's constants), 0 for anything else
+int sgm_mode_paths(int mode) {
+    switch (mode) {
+    case SD_SGM_MODE_3WAY: return 3;
+    case SD_SGM_MODE_HH4: return 4;
+    case SD_SGM_MODE_SGBM: return 5;
+    case SD_SGM_MODE_HH: return 8;
+    default: return 0;
+    }
+}
 const char* sgm_params_error(const SgmParams& p) {
     if (p.minD < 0) return "min_disparity must be >= 0";
     if (p.D % 16 != 0 || p.D < 16 || p.D > 256) return "num_disparities must be a multiple of 16 in [16, 256]";
     if (p.bs % 2 == 0 || p.bs < 3 || p.bs > 11) return "block_size must be odd in [3, 11]";
     if (p.cap < 1 || p.cap > 63) return "pre_filter_cap must be in [1, 63]";
     if (p.P1 < 0 || p.P2 < p.P1) return "0 <= P1 <= P2 required";
-    if (3ll * ((long long)p.bs * p.bs * (2 * p.cap + 63) + p.P2) > 65535) return "3 * (bs^2 * (2 * cap + 63) + P2) exceeds 65535";
+    if ((long long)p.npaths * ((long long)p.bs * p.bs * (2 * p.cap + 63) + p.P2) > 65535)
+        return p.npaths == 3   ? "3 * (bs^2 * (2 * cap + 63) + P2) exceeds 65535"
+               : p.npaths == 4 ? "4 * (bs^2 * (2 * cap + 63) + P2) exceeds 65535 (4 paths)"
+               : p.npaths == 5 ? "5 * (bs^2 * (2 * cap + 63) + P2) exceeds 65535 (5 paths)"
+                               : "8 * (bs^2 * (2 * cap + 63) + P2) exceeds 65535 (8 paths)";
     if (p.uniq < 0 || p.uniq > 100) return "uniqueness_ratio must be in [0, 100]";
     if (p.speckle_window < 0 || p.speckle_range < 0 || p.speckle_range > 1024) return "bad speckle parameters";
     return nullptr;
@@ -296,6 +313,104 @@ __global__ __launch_bounds__(64) void k_sgm_right(const uint16_t* __restrict__ C
 #pragma unroll
             for (int k = 0; k < NK; ++k) sc[k] = rs[j][k] + L[k];
             st_vol<NK, FULL>(s + (size_t)(t + j) * D, lane, D, sc);
+        }
+}
+
+// The further paths of the 4-, 5- and 8-path modes, and any single path of sd_sgm_aggregate_dir: one wave per scan
+// line, walking (y, x) += (dy, dx) with x taken modulo n = W - maxD. Vertical family (dy = +-1): wave c starts in column
+// c of the first (last) row and takes T = H steps, so at every step the n waves cover the n columns of one row once, a
+// diagonal that leaves the image on one side re-enters on the other as a new path (L back to the path-start state),
+// and no wave ever needs another's L. Left -> right (dy = 0, dx = 1): wave r walks row r, T = n. Each pixel is visited
+// once per launch, by one wave, so S = L or S += L is a plain store and the S of step t + SGM_PF can be read ahead.
+// One wave alone on its SIMD issues an instruction every four cycles, scalar ones included, so the walk is kept to a
+// few scalar instructions per step: a cursor is a 64-bit element offset that advances by one of two precomputed
+// increments (a plain move, or one that wraps in x) and the column it is in. The ring's cursor stops on the last step,
+// as the clamped reloads of the other passes do.
+struct SgmWalk {  // wave-uniform constants of a launch
+    long long inc, inc_wrap;
+    int dx, wrap_at, wrap_to;
+};
+struct SgmCursor {
+    long long off;
+    int x;
+};
+__device__ __forceinline__ void walk_advance(SgmCursor& c, const SgmWalk& w, bool go) {
+    const int nx = c.x + w.dx;
+    const bool wrap = nx == w.wrap_at;
+    const long long inc = wrap ? w.inc_wrap : w.inc;
+    c.off += go ? inc : 0;
+    c.x = go ? (wrap ? w.wrap_to : nx) : c.x;
+}
+template <int NK, bool FULL, bool ACC>
+__global__ __launch_bounds__(256) void k_sgm_walk(const uint16_t* __restrict__ C, int H, int W, int maxD, int D, int P1,
+                                                  int P2, int dy, int dx, int lines, int T, uint16_t* __restrict__ S) {
+    const int lane = threadIdx.x & 63;
+    const int line = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (line >= lines) return;
+    const int n = W - maxD;
+    const long long pitch = (long long)W * D;
+    const uint16_t* c = C + (size_t)maxD * D;
+    uint16_t* s = S + (size_t)maxD * D;
+    SgmWalk w;
+    w.dx = dx;
+    w.inc = dy * pitch + dx * D;
+    w.inc_wrap = w.inc - dx * (long long)n * D;
+    w.wrap_at = dx > 0 ? n : -1;  // dx == 0: never reached
+    w.wrap_to = dx > 0 ? 0 : n - 1;
+    const int y0 = dy == 0 ? line : (dy > 0 ? 0 : H - 1), x0 = dy == 0 ? 0 : line;
+    const SgmCursor first = {y0 * pitch + (long long)x0 * D, x0};
+    const int xstart = dx > 0 ? 0 : (dx < 0 ? n - 1 : -1);  // the column in which a path that moves along x starts
+    int L[NK], L0[NK], rc[SGM_PF][NK], rs[ACC ? SGM_PF : 1][NK];
+    path_init<NK, FULL>(L0, lane, D);
+#pragma unroll
+    for (int k = 0; k < NK; ++k) L[k] = L0[k];
+    // the cursor runs SGM_PF steps ahead, with the loads; a step finds its own offset and column where its loads were
+    // issued from, in a ring of scalars (static slots of the unrolled loop: registers)
+    SgmCursor ld = first;
+    long long roff[SGM_PF];
+    int rx[SGM_PF];
+#pragma unroll
+    for (int j = 0; j < SGM_PF; ++j) {
+        ld_vol<NK, FULL>(c + ld.off, lane, D, rc[j]);
+        if (ACC) ld_vol<NK, FULL>(s + ld.off, lane, D, rs[j]);
+        roff[j] = ld.off, rx[j] = ld.x;
+        walk_advance(ld, w, j + 1 < T);
+    }
+    int t = 0;
+    for (; t + SGM_PF <= T; t += SGM_PF) {
+#pragma unroll
+        for (int j = 0; j < SGM_PF; ++j) {
+            int cc[NK], sc[NK];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                cc[k] = rc[j][k];
+                sc[k] = ACC ? rs[ACC ? j : 0][k] : 0;
+            }
+            const long long off = roff[j];
+            const bool start = rx[j] == xstart;
+            ld_vol<NK, FULL>(c + ld.off, lane, D, rc[j]);
+            if (ACC) ld_vol<NK, FULL>(s + ld.off, lane, D, rs[ACC ? j : 0]);
+            roff[j] = ld.off, rx[j] = ld.x;
+            walk_advance(ld, w, t + j + SGM_PF + 1 < T);
+#pragma unroll
+            for (int k = 0; k < NK; ++k) L[k] = start ? L0[k] : L[k];
+            path_step<NK, FULL>(L, cc, lane, D, P1, P2);
+#pragma unroll
+            for (int k = 0; k < NK; ++k) sc[k] += L[k];
+            st_vol<NK, FULL>(s + off, lane, D, sc);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < SGM_PF; ++j)
+        if (t + j < T) {
+            int sc[NK];
+            const bool start = rx[j] == xstart;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) L[k] = start ? L0[k] : L[k];
+            path_step<NK, FULL>(L, rc[j], lane, D, P1, P2);
+#pragma unroll
+            for (int k = 0; k < NK; ++k) sc[k] = (ACC ? rs[ACC ? j : 0][k] : 0) + L[k];
+            st_vol<NK, FULL>(s + roff[j], lane, D, sc);
         }
 }
 
@@ -709,6 +824,39 @@ int launch_aggregate(int pass, const uint16_t* C, int H, int W, const SgmParams&
 }
 
 template <int NK, bool FULL>
+void launch_walk(const uint16_t* C, int H, int W, const SgmParams& p, int dy, int dx, bool acc, uint16_t* S,
+                 hipStream_t st) {
+    const int maxD = p.minD + p.D, n = W - maxD;
+    const int lines = dy == 0 ? H : n, T = dy == 0 ? n : H;
+    if (acc)
+        hipLaunchKernelGGL((k_sgm_walk<NK, FULL, true>), dim3(cdiv(lines, 4)), dim3(256), 0, st, C, H, W, maxD, p.D, p.P1,
+                           p.P2, dy, dx, lines, T, S);
+    else
+        hipLaunchKernelGGL((k_sgm_walk<NK, FULL, false>), dim3(cdiv(lines, 4)), dim3(256), 0, st, C, H, W, maxD, p.D, p.P1,
+                           p.P2, dy, dx, lines, T, S);
+}
+// one path (dy, dx) other than right -> left: S = L (acc false) or S += L. Top -> down writing S and left -> right
+// adding to it are the 3-way mode's own kernels.
+int launch_dir(const uint16_t* C, int H, int W, const SgmParams& p, int dy, int dx, bool acc, uint16_t* S,
+               hipStream_t st) {
+    if (W <= p.minD + p.D) return SD_OK;
+    if (dy == 1 && dx == 0 && !acc) return launch_aggregate(0, C, H, W, p, S, st);
+    if (dy == 0 && dx == 1 && acc) return launch_aggregate(1, C, H, W, p, S, st);
+    const bool full = p.D % 64 == 0;
+#define SGM_WALK(NK)                                                      \
+    (full ? launch_walk<NK, true>(C, H, W, p, dy, dx, acc, S, st)        \
+          : launch_walk<NK, false>(C, H, W, p, dy, dx, acc, S, st))
+    switch ((p.D + 63) / 64) {
+    case 1: SGM_WALK(1); break;
+    case 2: SGM_WALK(2); break;
+    case 3: SGM_WALK(3); break;
+    default: SGM_WALK(4); break;
+    }
+#undef SGM_WALK
+    return sd_check_launch("sd_sgm_aggregate_dir");
+}
+
+template <int NK, bool FULL>
 void launch_left(const uint16_t* C, const uint16_t* S, int H, int W, const SgmParams& p, uint16_t* S_total,
                  int16_t* q_raw, int16_t* q, hipStream_t st) {
     const size_t lds = (size_t)(W + 1) * 14;
@@ -800,6 +948,20 @@ extern "C" int sd_sgm_aggregate(const uint16_t* C, int H, int W, int min_dispari
     return launch_aggregate(pass, C, H, W, p, S, to_stream(s));
 }
 
+extern "C" int sd_sgm_aggregate_dir(const uint16_t* C, int H, int W, int min_disparity, int num_disparities, int P1,
+                                    int P2, int dy, int dx, int accumulate, uint16_t* S, sd_stream s) {
+    SD_REQUIRE(C && S, "sd_sgm_aggregate_dir: null pointer");
+    SD_REQUIRE(sgm_dims_ok(H, W), "sd_sgm_aggregate_dir: bad sizes %dx%d", H, W);
+    SD_REQUIRE(!(dy == 0 && dx == -1),
+               "sd_sgm_aggregate_dir: the right -> left path (0, -1) runs inside sd_sgm_winner, on top of the other paths' S");
+    SD_REQUIRE(((dy == 1 || dy == -1) && dx >= -1 && dx <= 1) || (dy == 0 && dx == 1),
+               "sd_sgm_aggregate_dir: direction (%d, %d): dy = +-1 with dx in {-1, 0, 1}, or (0, 1)", dy, dx);
+    SD_REQUIRE(accumulate == 0 || accumulate == 1, "sd_sgm_aggregate_dir: accumulate %d (0: S = L, 1: S += L)", accumulate);
+    const SgmParams p = {min_disparity, num_disparities, 3, P1, P2, 1, 0, 0, 0, 1};
+    SGM_PARAMS_OK("sd_sgm_aggregate_dir", p);
+    return launch_dir(C, H, W, p, dy, dx, accumulate != 0, S, to_stream(s));
+}
+
 extern "C" int sd_sgm_winner(const uint16_t* C, const uint16_t* S, int H, int W, int min_disparity, int num_disparities,
                              int P1, int P2, int uniqueness_ratio, int disp12_max_diff, uint16_t* S_total,
                              int16_t* q_raw, int16_t* q, sd_stream s) {
@@ -819,17 +981,16 @@ extern "C" int sd_sgm_speckle(int16_t* q, int H, int W, int invalid_value, int w
     return launch_speckle(q, H, W, invalid_value, window, range, work, to_stream(s));
 }
 
-extern "C" int sd_sgm_compute(const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
-                              int num_disparities, int block_size, int P1, int P2, int disp12_max_diff,
-                              int uniqueness_ratio, int speckle_window, int speckle_range, int pre_filter_cap, void* work,
-                              int16_t* q, sd_stream s) {
-    SD_REQUIRE(gray_l && gray_r && work && q, "sd_sgm_compute: null pointer");
-    SD_REQUIRE(sgm_dims_ok(H, W) && H <= 65535 && W <= SGM_MAX_W, "sd_sgm_compute: bad sizes %dx%d (W <= %d)", H, W,
-               SGM_MAX_W);
-    SD_REQUIRE((uintptr_t)work % 256 == 0, "sd_sgm_compute: work must be 256-B aligned");
-    const SgmParams p = {min_disparity, num_disparities, block_size, P1, P2, disp12_max_diff, uniqueness_ratio,
-                         speckle_window, speckle_range, pre_filter_cap};
-    SGM_PARAMS_OK("sd_sgm_compute", p);
+namespace {
+// the vertical-family paths a mode adds to the 3-way mode's three, as (dy, dx)
+const int SGM_EXTRA_PATHS[5][2] = {{1, 1}, {1, -1}, {-1, 0}, {-1, 1}, {-1, -1}};
+int sgm_compute(const char* what, const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, const SgmParams& p,
+                int mode, void* work, int16_t* q, sd_stream s) {
+    SD_REQUIRE(gray_l && gray_r && work && q, "%s: null pointer", what);
+    SD_REQUIRE(sgm_dims_ok(H, W) && H <= 65535 && W <= SGM_MAX_W, "%s: bad sizes %dx%d (W <= %d)", what, H, W, SGM_MAX_W);
+    SD_REQUIRE((uintptr_t)work % 256 == 0, "%s: work must be 256-B aligned", what);
+    const char* e = sgm_params_error(p);
+    SD_REQUIRE(!e, "%s: %s", what, e);
     const long long P = (long long)H * W, vol = align256(2 * P * p.D);
     char* w = static_cast<char*>(work);
     uint16_t* C = reinterpret_cast<uint16_t*>(w);
@@ -843,10 +1004,36 @@ extern "C" int sd_sgm_compute(const uint8_t* gray_l, const uint8_t* gray_r, int 
     hipLaunchKernelGGL(k_sgm_prefilter, g, b, 0, st, gray_r, H, W, p.cap, pr);
     int rc = launch_cost(gray_l, gray_r, pl, pr, H, W, p, C, S, st);  // S is free until the first path writes it
     if (rc == SD_OK) rc = launch_aggregate(0, C, H, W, p, S, st);
+    // successive launches, each S += L: sgbm takes the two downward diagonals, hh4 bottom -> up, hh all five
+    const int first = mode == SD_SGM_MODE_HH4 ? 2 : 0;
+    const int last = mode == SD_SGM_MODE_HH4 ? 3 : mode == SD_SGM_MODE_SGBM ? 2 : mode == SD_SGM_MODE_HH ? 5 : 0;
+    for (int i = first; i < last && rc == SD_OK; ++i)
+        rc = launch_dir(C, H, W, p, SGM_EXTRA_PATHS[i][0], SGM_EXTRA_PATHS[i][1], true, S, st);
     if (rc == SD_OK) rc = launch_aggregate(1, C, H, W, p, S, st);
     if (rc == SD_OK) rc = launch_winner(C, S, H, W, p, nullptr, nullptr, q, st);
     if (rc == SD_OK) rc = launch_speckle(q, H, W, 16 * (p.minD - 1), p.speckle_window, p.speckle_range, sw, st);
     return rc;
+}
+}  // namespace
+
+extern "C" int sd_sgm_compute(const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
+                              int num_disparities, int block_size, int P1, int P2, int disp12_max_diff,
+                              int uniqueness_ratio, int speckle_window, int speckle_range, int pre_filter_cap, void* work,
+                              int16_t* q, sd_stream s) {
+    const SgmParams p = {min_disparity, num_disparities, block_size, P1, P2, disp12_max_diff, uniqueness_ratio,
+                         speckle_window, speckle_range, pre_filter_cap};
+    return sgm_compute("sd_sgm_compute", gray_l, gray_r, H, W, p, SD_SGM_MODE_3WAY, work, q, s);
+}
+
+extern "C" int sd_sgm_compute_mode(const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
+                                   int num_disparities, int block_size, int P1, int P2, int disp12_max_diff,
+                                   int uniqueness_ratio, int speckle_window, int speckle_range, int pre_filter_cap,
+                                   int mode, void* work, int16_t* q, sd_stream s) {
+    const int npaths = sgm_mode_paths(mode);
+    SD_REQUIRE(npaths, "sd_sgm_compute_mode: mode %d (SD_SGM_MODE_SGBM 0, _HH 1, _3WAY 2, _HH4 3)", mode);
+    const SgmParams p = {min_disparity, num_disparities, block_size, P1, P2, disp12_max_diff, uniqueness_ratio,
+                         speckle_window, speckle_range, pre_filter_cap, npaths};
+    return sgm_compute("sd_sgm_compute_mode", gray_l, gray_r, H, W, p, mode, work, q, s);
 }
 
 extern "C" int sd_sgm_post(const int16_t* q, int H, int W, const double* Q, float* disp, float* z, uint8_t* code,

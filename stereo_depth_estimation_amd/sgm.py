@@ -8,9 +8,10 @@ and text): rectification, gray, a semi-global matcher, reprojection, the centre 
     res = classic.step(frame_l, frame_r)       # no host sync: device tensors, overwritten by the next step
     dist_m = res.readout()                     # the only host sync (4 bytes)
 
-The matcher follows OpenCV's StereoSGBM step by step (three paths) and is pinned bit for bit to the NumPy restatement
-tests/sgm_ref.py, not to cv2's bytes; what is stated rather than taken from OpenCV is listed in INTEGRATION.md. Kernels:
-csrc/sgm.hip. There is no CPU fallback.
+The matcher follows OpenCV's StereoSGBM step by step (three paths by default; mode="hh4" / "sgbm" / "hh" add the
+bottom-up path, the two downward diagonals or all eight) and is pinned bit for bit to the NumPy restatements
+tests/sgm_ref.py and tests/sgm_modes_ref.py, not to cv2's bytes; what is stated rather than taken from OpenCV is
+listed in INTEGRATION.md. Kernels: csrc/sgm.hip. There is no CPU fallback.
 """
 
 from __future__ import annotations
@@ -22,6 +23,23 @@ from . import _lib as L
 from .live import MAX_CENTER_WINDOW, colormap_lut
 
 MAX_WIDTH = 4096  # the winner kernel keeps a row's right-view state in LDS
+
+# mode name -> (cv2.StereoSGBM constant = SD_SGM_MODE_*, paths summed into S)
+MODES = {"3way": (L.SD_SGM_MODE_3WAY, 3), "hh4": (L.SD_SGM_MODE_HH4, 4), "sgbm": (L.SD_SGM_MODE_SGBM, 5),
+         "hh": (L.SD_SGM_MODE_HH, 8)}
+
+
+def mode_name(mode) -> str:
+    """One of MODES' names from a name or from cv2's integer constant (MODE_SGBM 0, MODE_HH 1, MODE_SGBM_3WAY 2,
+    MODE_HH4 3)."""
+    if isinstance(mode, str) and mode in MODES:
+        return mode
+    if isinstance(mode, (int, np.integer)) and not isinstance(mode, bool):
+        for name, (const, _) in MODES.items():
+            if const == int(mode):
+                return name
+    raise ValueError(f"mode must be one of {sorted(MODES)} or cv2's constants 0 (sgbm), 1 (hh), 2 (3way), 3 (hh4), "
+                     f"got {mode!r}")
 
 
 def ws_bytes(H: int, W: int, D: int) -> int:
@@ -46,10 +64,13 @@ def reprojection_rows(Q) -> np.ndarray:
 
 
 class StereoSGM:
-    """cv2.StereoSGBM.create(..., mode=MODE_SGBM_3WAY) of depth_live.py:67-83, parameters by the same names."""
+    """cv2.StereoSGBM.create(..., mode=MODE_SGBM_3WAY) of depth_live.py:67-83, parameters by the same names. mode: "3way"
+    (the application's), "hh4", "sgbm" or "hh", or cv2's integer constant."""
 
     def __init__(self, min_disparity=0, num_disparities=128, block_size=7, P1=None, P2=None, disp12_max_diff=1,
-                 uniqueness_ratio=10, speckle_window_size=100, speckle_range=2, pre_filter_cap=31):
+                 uniqueness_ratio=10, speckle_window_size=100, speckle_range=2, pre_filter_cap=31, mode="3way"):
+        self.mode = mode_name(mode)
+        self.mode_id, npaths = MODES[self.mode]
         minD, D, bs = int(min_disparity), int(num_disparities), int(block_size)
         if D % 16 != 0:
             raise ValueError("--num-disparities must be a multiple of 16.")
@@ -68,9 +89,10 @@ class StereoSGM:
             raise ValueError("pre_filter_cap must be in [1, 63]")
         if P1 < 0 or P2 < P1:
             raise ValueError("0 <= P1 <= P2 required")
-        if 3 * (bs * bs * (2 * cap + 63) + P2) > 65535:
-            raise ValueError(f"3 * (block_size^2 * (2 * pre_filter_cap + 63) + P2) = "
-                             f"{3 * (bs * bs * (2 * cap + 63) + P2)} exceeds 65535: the cost sums would not fit uint16")
+        if npaths * (bs * bs * (2 * cap + 63) + P2) > 65535:
+            raise ValueError(f"{npaths} * (block_size^2 * (2 * pre_filter_cap + 63) + P2) = "
+                             f"{npaths * (bs * bs * (2 * cap + 63) + P2)} exceeds 65535: the cost sums of the "
+                             f"{npaths} paths of mode {self.mode!r} would not fit uint16")
         if not 0 <= int(uniqueness_ratio) <= 100:
             raise ValueError("uniqueness_ratio must be in [0, 100]")
         if int(speckle_window_size) < 0 or not 0 <= int(speckle_range) <= 1024:
@@ -87,7 +109,7 @@ class StereoSGM:
         return 16 * (self.min_disparity - 1)
 
     def params(self) -> tuple:
-        """The integer arguments of sd_sgm_compute, in its order."""
+        """The integer arguments of sd_sgm_compute, in its order (sd_sgm_compute_mode takes mode_id after them)."""
         return (self.min_disparity, self.num_disparities, self.block_size, self.P1, self.P2, self.disp12_max_diff,
                 self.uniqueness_ratio, self.speckle_window_size, self.speckle_range, self.pre_filter_cap)
 
@@ -119,8 +141,12 @@ class StereoSGM:
             raise ValueError("out must be a contiguous int16 [H, W] tensor on the images' device")
         ws = self.workspace(gray_l.device, H, W)
         with torch.cuda.device(gray_l.device):
-            L.call("sd_sgm_compute", gray_l.data_ptr(), gray_r.data_ptr(), H, W, *self.params(), ws.data_ptr(),
-                   out.data_ptr(), L.stream_handle(gray_l.device))
+            if self.mode == "3way":
+                L.call("sd_sgm_compute", gray_l.data_ptr(), gray_r.data_ptr(), H, W, *self.params(), ws.data_ptr(),
+                       out.data_ptr(), L.stream_handle(gray_l.device))
+            else:
+                L.call("sd_sgm_compute_mode", gray_l.data_ptr(), gray_r.data_ptr(), H, W, *self.params(), self.mode_id,
+                       ws.data_ptr(), out.data_ptr(), L.stream_handle(gray_l.device))
         return out
 
 

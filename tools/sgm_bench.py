@@ -7,9 +7,11 @@ The matcher's reference points are arithmetic, not measurements: the two uint16 
 2 * H * W * D bytes. The three recurrences move seven of them (top-down reads C, writes S; left-right reads C and S,
 writes S; right-left reads C and S), and each is one sequential chain of H or W - maxD steps per scan line; the cost
 stage writes its row sums into S as scratch, reads them about twice and writes C. The table prints the volume bytes
-over each stage's time next to the chain's time per step.
+over each stage's time next to the chain's time per step. --mode hh4 / sgbm / hh runs the frame with that mode's
+further paths (each one launch that reads C and S and writes S: three volumes, H steps per chain) and times each of
+them alone, with top -> down as an adding pass of the same kernel beside them.
 
-    python tools/sgm_bench.py --frames 640x480 --num-disparities 128 --block-size 7 --json out.json
+    python tools/sgm_bench.py --frames 640x480 --num-disparities 128 --block-size 7 --mode hh --json out.json
 """
 
 from __future__ import annotations
@@ -81,11 +83,16 @@ def _scene(rng, wc: int, hc: int):
     return frames, rect, Q
 
 
-def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int) -> dict:
+# the vertical-family paths a mode adds to the three of "3way", in the order sd_sgm_compute_mode launches them
+EXTRA_PATHS = {"3way": (), "hh4": ((-1, 0),), "sgbm": ((1, 1), (1, -1)),
+               "hh": ((1, 1), (1, -1), (-1, 0), (-1, 1), (-1, -1))}
+
+
+def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str = "3way") -> dict:
     dev = torch.device("cuda", torch.cuda.current_device())
     (fl, fr), rect, Q = _scene(np.random.default_rng(0), wc, hc)
-    cd = sgm.ClassicDepth(rectification=rect, Q=Q, num_disparities=D, block_size=bs, device=dev)
-    out = {"frames": f"{wc}x{hc}", "num_disparities": D, "block_size": bs, "iters": iters, "warmup": warmup,
+    cd = sgm.ClassicDepth(rectification=rect, Q=Q, num_disparities=D, block_size=bs, mode=mode, device=dev)
+    out = {"frames": f"{wc}x{hc}", "num_disparities": D, "block_size": bs, "mode": mode, "iters": iters, "warmup": warmup,
            "clock_mhz_before": clock_probe(dev)}
 
     def frame():
@@ -124,6 +131,8 @@ def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int) -> dict:
                                                         m.uniqueness_ratio, m.disp12_max_diff, None, None,
                                                         q_tmp.data_ptr(), s),
         "aggregate left-right": lambda: L.call("sd_sgm_aggregate", *agg, 1, S, s),
+        **{f"aggregate ({dy:+d}, {dx:+d}) adding": (lambda dy=dy, dx=dx: L.call("sd_sgm_aggregate_dir", *agg, dy, dx, 1, S, s))
+           for dy, dx in (((1, 0),) + EXTRA_PATHS[mode] if mode != "3way" else ())},
         "speckle": lambda: (q_tmp.copy_(q), L.call("sd_sgm_speckle", q_tmp.data_ptr(), H, W, m.invalid_value,
                                                    m.speckle_window_size, m.speckle_range, sw, s)),
         "post": lambda: L.call("sd_sgm_post", q.data_ptr(), H, W, cd.Q.ctypes.data, b["disp"].data_ptr(),
@@ -132,19 +141,26 @@ def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int) -> dict:
         "compose": lambda: L.call("sd_live_compose", b["code"].data_ptr(), b["lut"].data_ptr(), b["vis"].data_ptr(),
                                   None, None, None, None, None, None, H, W, H, W, s),
     }
-    # the left-right pass adds into S on every launch, so it is timed after the winner kernel (which reads S)
+    # the left-right pass and a mode's further paths add into S on every launch, so they are timed after the winner
+    # kernel (which reads S)
     out["stage_us"] = {k: 1e3 * _events(fn, iters, warmup)[0] for k, fn in stages.items()}
     out["stages_ms_sum"] = sum(out["stage_us"].values()) / 1e3
     volume_bytes = 2 * P * D
     passes = {"cost": 1, "aggregate top-down": 2, "aggregate left-right": 3, "aggregate right-left + winner": 2}
+    extra = [k for k in stages if k.endswith("adding")]
+    passes.update({k: 3 for k in extra})
     out["volume_bytes"] = volume_bytes
     out["volume_GBps"] = {k: n * volume_bytes / (out["stage_us"][k] * 1e-6) / 1e9 for k, n in passes.items()}
     maxD = m.min_disparity + D
     steps = {"aggregate top-down": H, "aggregate left-right": W - maxD, "aggregate right-left + winner": W - maxD}
     out["chain_ns_per_step"] = {k: out["stage_us"][k] * 1e3 / n for k, n in steps.items()}
-    agg_us = sum(out["stage_us"][k] for k in steps)
+    out["chain_ns_per_step"].update({k: out["stage_us"][k] * 1e3 / H for k in extra})
+    # the frame's own aggregation: the three passes and the mode's further paths (not the adding top-down pass,
+    # which is there for comparison only)
+    own = list(steps) + [k for k in extra if not k.startswith("aggregate (+1, +0)")]
+    agg_us = sum(out["stage_us"][k] for k in own)
     out["aggregate_ms"] = agg_us / 1e3
-    out["aggregate_volume_GBps"] = 7 * volume_bytes / (agg_us * 1e-6) / 1e9
+    out["aggregate_volume_GBps"] = sum(passes[k] for k in own) * volume_bytes / (agg_us * 1e-6) / 1e9
     out["clock_mhz_after"] = clock_probe(dev)
     return out
 
@@ -154,6 +170,7 @@ def main() -> None:
     ap.add_argument("--frames", default="640x480")
     ap.add_argument("--num-disparities", type=int, default=128)
     ap.add_argument("--block-size", type=int, default=7)
+    ap.add_argument("--mode", choices=sorted(sgm.MODES), default="3way")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--json", type=Path, default=None)
@@ -161,9 +178,9 @@ def main() -> None:
     if not torch.cuda.is_available():
         raise SystemExit("sgm_bench needs a HIP device: there is no CPU fallback and no CPU timing")
     w, h = (int(v) for v in args.frames.lower().split("x"))
-    r = bench(w, h, args.num_disparities, args.block_size, args.iters, args.warmup)
+    r = bench(w, h, args.num_disparities, args.block_size, args.iters, args.warmup, args.mode)
     print(json.dumps(r), flush=True)
-    print(f"\nframe {r['frames']}, D = {r['num_disparities']}, bs = {r['block_size']}: "
+    print(f"\nframe {r['frames']}, D = {r['num_disparities']}, bs = {r['block_size']}, mode {r['mode']}: "
           f"{r['frame_ms_events']:.3f} ms (events) / {r['frame_ms_wall']:.3f} ms (wall) per step + readout; "
           f"clock {r['clock_mhz_before']} / {r['clock_mhz_after']} MHz; valid {r['valid_fraction']:.2f}")
     print("\n| stage | us | volume GB/s | ns per chain step |\n|---|---|---|---|")
