@@ -451,6 +451,56 @@ int sd_live_compose(const uint8_t* code_a, const uint8_t* lut_a, uint8_t* vis_a,
                     const uint8_t* lut_b, uint8_t* vis_b, const uint8_t* edge, const uint8_t* view, uint8_t* left_view,
                     int H, int W, int Hc, int Wc, sd_stream s);
 
+/* ---- the same frame path for n camera pairs per launch (1 <= n <= 64) ----
+ * One entry point per stage above. Every buffer is stream-major: [n] of the single-stream layout, stream i's slice at
+ * i * (the single-stream element count); the colour tables, the scalars of the colour ranges and the EMA weights are
+ * shared. Each entry point issues as many launches as its single-stream form issues for one stream (the stream is a
+ * grid dimension), and stream i's outputs are bit-identical to the single-stream entry point run on stream i's slices.
+ * The 16-B / 4-B vector paths are taken only when every slice is aligned for them (the per-stream element count a
+ * multiple of 4 and the base pointers aligned), so H * W or Hc * Wc * 3 need not be a multiple of anything.
+ * Masks are passed by value, bit i for stream i; a bit at or above n is an error.
+ *   hold_mask : stream i had no new frame: the entry point reads and writes nothing of stream i (its state, maps,
+ *               codes, images, sel row, centre row and select workspace stay as they are)
+ *   copy_mask : (post) stream i's EMA state takes the prediction as is (first frame, reset, or alpha 0)
+ * The front end and the rectified view take no mask: they run over whatever the frame slots hold.
+ * Arguments are checked before any launch; no allocation, no synchronisation, graph-capturable.
+ *
+ * Front end. left, right: u8 [n][Hc][Wc][3]. Maps: NULL, or map1 int16 [m][Hc][Wc][2] / map2 uint16 [m][Hc][Wc] with
+ * map_stride = 0 (m = 1: one set shared by all streams) or Hc * Wc (m = n: one set per stream), the same for both
+ * sides. xin: [n][H][W][8] (the engine's batch-n input, = sd_pack_input(dtype, nchw, n, 6, H, W, 8, xin)); nchw:
+ * optional f32 [n][6][H][W]. amax: as sd_live_frontend, the maximum taken over all streams, amax[clear] zeroed once. */
+int sd_live_frontend_n(int n, int dtype, const uint8_t* left, const uint8_t* right, int Hc, int Wc,
+                       const int16_t* map1_l, const uint16_t* map2_l, const int16_t* map1_r, const uint16_t* map2_r,
+                       long long map_stride, int H, int W, void* xin, float* nchw, unsigned* amax, int slot, int clear,
+                       sd_stream s);
+/* Rectified views: frames, views u8 [n][Hc][Wc][3]; maps and map_stride as above (both maps required). */
+int sd_live_rectify_n(int n, const uint8_t* frames, int Hc, int Wc, const int16_t* map1, const uint16_t* map2,
+                      long long map_stride, uint8_t* views, sd_stream s);
+/* Post stage: disp, logvar, state, depth, conf f32 [n][H][W]; depth_code, conf_code u8 [n][H][W]; focal_baseline: a
+ * DEVICE array of n float32 (read when depth_on; depth is on for all streams or for none). Optional buffers as in
+ * sd_live_post. */
+int sd_live_post_n(int n, const float* disp, const float* logvar, int H, int W, float* state,
+                   unsigned long long copy_mask, unsigned long long hold_mask, float alpha, float one_minus_alpha,
+                   int depth_on, const float* focal_baseline, float* depth, float* conf, uint8_t* depth_code,
+                   float depth_lo, float depth_scale, uint8_t* conf_code, float conf_lo, float conf_scale, sd_stream s);
+/* Contours: depth f32 [n][H][W] -> edge u8 [n][H][W]. */
+int sd_live_contours_n(int n, const float* depth, int H, int W, float min_depth, float max_depth, float step,
+                       uint8_t* edge, unsigned long long hold_mask, sd_stream s);
+/* Auto range per stream: values f32 [n][H][W], sel f32 [n][8] (row i: the 7 words of sd_live_select for stream i; a
+ * stream without a finite positive value gets NaN and all-zero codes), code optional u8 [n][H][W]. work:
+ * sd_live_select_n_ws_bytes(n) bytes (n single-stream workspaces; -1 for n outside 1..64), zero before the first call;
+ * every call leaves every stream's part zero. Seven launches (six without code), as sd_live_select. */
+long long sd_live_select_n_ws_bytes(int n);
+int sd_live_select_n(int n, const float* values, int H, int W, unsigned* work, float* sel, uint8_t* code,
+                     unsigned long long hold_mask, sd_stream s);
+/* Centre medians: disp, depth, conf f32 [n][H][W] (depth, conf optional) -> out3 f32 [n][3]. One launch. */
+int sd_live_center_n(int n, const float* disp, const float* depth, const float* conf, int H, int W, int window,
+                     float* out3, unsigned long long hold_mask, sd_stream s);
+/* Display images: code_x, edge u8 [n][H][W]; vis_x, view, left_view u8 [n][Hc][Wc][3]; lut_x u8 [256][3], shared. */
+int sd_live_compose_n(int n, const uint8_t* code_a, const uint8_t* lut_a, uint8_t* vis_a, const uint8_t* code_b,
+                      const uint8_t* lut_b, uint8_t* vis_b, const uint8_t* edge, const uint8_t* view, uint8_t* left_view,
+                      int H, int W, int Hc, int Wc, unsigned long long hold_mask, sd_stream s);
+
 /* ---- semi-global matcher of the classical live loop (live_camera/depth_live.py:67-83 build_matcher, :158-178) ----
  * The algorithm is stated in INTEGRATION.md ("The semi-global matcher"): OpenCV's StereoSGBM step by step with three
  * paths, integer arithmetic up to the int16 disparity (16 * d, invalid = 16 * (min_disparity - 1)), pinned to the NumPy

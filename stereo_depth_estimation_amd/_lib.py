@@ -27,6 +27,7 @@ SD_SGM_MODE_SGBM, SD_SGM_MODE_HH, SD_SGM_MODE_3WAY, SD_SGM_MODE_HH4 = 0, 1, 2, 3
 _p = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
+_u64 = ctypes.c_uint64
 _f = ctypes.c_float
 _d = ctypes.c_double
 
@@ -189,6 +190,16 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_live_select": (_i, [_p, _i, _i, _p, _p, _p, _p]),
     "sd_live_center": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
     "sd_live_compose": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    # the same stages for n streams: n first, masks as uint64 by value
+    "sd_live_frontend_n": (_i, [_i, _i, _p, _p, _i, _i, _p, _p, _p, _p, ctypes.c_longlong, _i, _i, _p, _p, _p, _i, _i,
+                                _p]),
+    "sd_live_rectify_n": (_i, [_i, _p, _i, _i, _p, _p, ctypes.c_longlong, _p, _p]),
+    "sd_live_post_n": (_i, [_i, _p, _p, _i, _i, _p, _u64, _u64, _f, _f, _i, _p, _p, _p, _p, _f, _f, _p, _f, _f, _p]),
+    "sd_live_contours_n": (_i, [_i, _p, _i, _i, _f, _f, _f, _p, _u64, _p]),
+    "sd_live_select_n_ws_bytes": (ctypes.c_longlong, [_i]),
+    "sd_live_select_n": (_i, [_i, _p, _i, _i, _p, _p, _p, _u64, _p]),
+    "sd_live_center_n": (_i, [_i, _p, _p, _p, _i, _i, _i, _p, _u64, _p]),
+    "sd_live_compose_n": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _u64, _p]),
     "sd_sgm_gray": (_i, [_p, _i, _i, _p, _p]),
     "sd_sgm_prefilter": (_i, [_p, _i, _i, _i, _p, _p]),
     "sd_sgm_cost": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),

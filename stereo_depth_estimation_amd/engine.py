@@ -783,14 +783,16 @@ class UNetEngine:
 
         return self._forward(B, H, W, train, need_backward, pack)
 
-    def forward_packed(self, H: int, W: int, pack):
-        """An eval forward (B = 1, no backward) whose input the caller packs itself: pack(xin_ptr, amax_ptr, slot,
-        clear, stream) must fill the workspace's NHWC input (cin_pad0 channels, the engine's dtype) on `stream`, as
-        sd_pack_input would, and, when amax_ptr is not None, follow sd_pack_input_amax's protocol for amax[slot] /
-        amax[clear] (the static fp8 path's range check; otherwise slot = 0, clear = -1). Everything after the pack,
-        graph replay included, is forward()'s."""
+    def forward_packed(self, H: int, W: int, pack, batch: int = 1):
+        """An eval forward (B = batch, no backward) whose input the caller packs itself: pack(xin_ptr, amax_ptr, slot,
+        clear, stream) must fill the workspace's NHWC input ([batch][H][W] pixels of cin_pad0 channels, the engine's
+        dtype) on `stream`, as sd_pack_input would, and, when amax_ptr is not None, follow sd_pack_input_amax's
+        protocol for amax[slot] / amax[clear] with the maximum over the whole batch (the static fp8 path's range check;
+        otherwise slot = 0, clear = -1). Everything after the pack, graph replay included, is forward()'s at that B."""
         if self.in_channels > self.cin_pad0:
             raise ValueError("forward_packed: the model's input does not fit the packed layout")
+        if int(batch) < 1:
+            raise ValueError("forward_packed: batch must be >= 1")
 
         def feed(ws):
             self._xin_ready = None
@@ -800,7 +802,7 @@ class UNetEngine:
             else:
                 pack(xin, None, 0, -1, self._s())
 
-        return self._forward(1, H, W, False, False, feed)
+        return self._forward(int(batch), H, W, False, False, feed)
 
     def _forward(self, B: int, H: int, W: int, train: bool, need_backward: bool | None, pack):
         """forward() after the input checks; pack(ws) fills ws.t["xin"]."""

@@ -10,6 +10,9 @@ HIP pass that writes the engine's input; EMA, depth, confidence, colour codes, c
 medians and the colour images run after the heads (csrc/live.hip). Camera capture, windows and text overlays stay with
 the host application. Not reproduced: OpenCV's intermediate uint8 rounding and fixed-point interpolation tables, and
 the bytes of its colormap tables.
+
+Several rigs of one capture size run through one step with LiveDepthBatch (below): one front end, one batch-N forward,
+one display stage and one read-out for N camera pairs.
 """
 
 from __future__ import annotations
@@ -367,3 +370,307 @@ class LiveDepth:
         torch.cuda.current_stream(self._key[0]).synchronize()
         c = b["center_host"]
         return float(c[0]), float(c[1]), float(c[2])
+
+
+# ---------------------------------------------------------------------- several rigs per step
+MAX_STREAMS = 64
+
+
+class LiveBatchResult:
+    """Device tensors of one LiveDepthBatch step, stream-major (views of its buffers: the next step overwrites them,
+    except the slices of streams it holds). depth_m, confidence and confidence_vis are None when depth / uncertainty
+    is off."""
+
+    __slots__ = ("disparity", "logvar", "depth_m", "confidence", "depth_vis", "confidence_vis", "left_view", "_live")
+
+    def __init__(self, live, **kw):
+        self._live = live
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def readout(self) -> np.ndarray:
+        """float32 [N, 3]: (center_disparity, center_depth_m, center_confidence) per stream as of the latest step
+        (a held stream's row is its last fresh frame's). One 12 * N-byte copy and the only host synchronisation."""
+        return self._live._readout()
+
+
+def _per_stream(value, streams: int, name: str) -> list:
+    """A scalar (or None) for all streams, or a sequence of one value per stream."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != streams:
+            raise ValueError(f"{name}: a sequence must have one entry per stream ({streams}), got {len(value)}")
+        return list(value)
+    return [value] * streams
+
+
+class LiveDepthBatch:
+    """LiveDepth for `streams` camera pairs of one capture size and one model: one front-end launch, one batch-N
+    forward and one launch sequence of the display stage per step, whatever N is.
+
+        live = LiveDepthBatch(model, streams=4, model_size=(960, 720), rectification=[rect0, rect1, rect2, rect3])
+        res = live.step(frames_l, frames_r, fresh=[True, True, False, True])   # stream 2 had no new frame
+        centers = res.readout()                                                # [4, 3], the only host sync
+
+    A stream that is not fresh is held: its EMA state, depth, confidence, images and centre row stay as its last
+    fresh frame left them. The forward still runs over all N input slots, and res.logvar (the heads' raw output, like
+    the raw disparity before the EMA) is overwritten for held streams too."""
+
+    def __init__(self, model, streams, model_size=(320, 240), rectification=None, focal_length_px=None, baseline_m=None,
+                 calibration_width_px=None, uncertainty=True, colormap="turbo", ema_alpha=0.0, center_window=15):
+        """streams: 1..64. rectification: None, one RectificationData-like object shared by all streams, or a sequence
+        of one per stream (all of one image_size); focal_length_px, baseline_m, calibration_width_px: scalars or
+        sequences of one per stream. Depth is enabled per stream by LiveDepth's rule, and must be enabled for all
+        streams or for none. Everything else as LiveDepth."""
+        n = int(streams)
+        if not 1 <= n <= MAX_STREAMS:
+            raise ValueError(f"streams must be in [1, {MAX_STREAMS}]")
+        if not 0.0 <= float(ema_alpha) <= 1.0:
+            raise ValueError("ema_alpha must be in [0, 1]")
+        if not 0 <= int(center_window) <= MAX_CENTER_WINDOW:
+            raise ValueError(f"center_window must be in [0, {MAX_CENTER_WINDOW}]")
+        if model.in_channels != 6:
+            raise ValueError("LiveDepthBatch needs a stereo model (in_channels 6)")
+        self.model = model
+        self.streams = n
+        self.W, self.H = int(model_size[0]), int(model_size[1])
+        if self.H % 16 or self.W % 16 or self.H <= 0 or self.W <= 0:
+            raise ValueError("model_size must be positive multiples of 16 (four 2x2 pools)")
+        self.shared_maps = not isinstance(rectification, (list, tuple))
+        rects = _per_stream(rectification, n, "rectification")
+        if rectification is not None and any(r is None for r in rects):
+            raise ValueError("rectification: a sequence must hold one object per stream (no None entries)")
+        sizes = {tuple(r.image_size) for r in rects if r is not None}
+        if len(sizes) > 1:
+            raise ValueError(f"rectification: all streams must have one image_size, got {sorted(sizes)}")
+        self.rectification = None if rectification is None else rects
+        self.image_size = sizes.pop() if sizes else None
+        focal = _per_stream(focal_length_px, n, "focal_length_px")
+        base = _per_stream(baseline_m, n, "baseline_m")
+        width = _per_stream(calibration_width_px, n, "calibration_width_px")
+        self.focal_length_px_model, self.baseline_m = [], []
+        for i, r in enumerate(rects):
+            f, b, w = (r.focal_length_px, r.baseline_m, r.image_size[0]) if r is not None else (focal[i], base[i], width[i])
+            fm = f * (self.W / float(w)) if f is not None and w is not None and w > 0 else None
+            self.focal_length_px_model.append(fm)
+            self.baseline_m.append(b)
+        enabled = [fm is not None and b is not None for fm, b in zip(self.focal_length_px_model, self.baseline_m)]
+        if any(enabled) != all(enabled):
+            raise ValueError("depth is enabled for some streams and not for others (a baseline and a focal length with "
+                             f"its calibration width per stream): enabled = {enabled}; it must be all or none")
+        self.depth_enabled = all(enabled)
+        self.uncertainty = bool(uncertainty)
+        self.ema_alpha = float(ema_alpha)
+        self.center_window = int(center_window)
+        lut = colormap_lut(colormap) if isinstance(colormap, str) else np.asarray(colormap)
+        if lut.shape != (256, 3) or lut.dtype != np.uint8:
+            raise ValueError("colormap: a name or a [256, 3] uint8 BGR table")
+        self._lut_host = (np.ascontiguousarray(lut), colormap_lut(CONFIDENCE_COLORMAP))
+        self._first = [True] * n  # the stream's next fresh frame is copied into the EMA state
+        self._seen = [False] * n  # the stream has had a fresh frame since the buffers were made
+        self._buf = None
+        self._key = None
+        self._stage_i = 0
+
+    def reset(self, stream=None) -> None:
+        """Forget the EMA state of one stream, or of all: its next fresh frame's prediction is taken as is."""
+        if stream is None:
+            self._first = [True] * self.streams
+            return
+        if not 0 <= int(stream) < self.streams:
+            raise ValueError(f"stream must be in [0, {self.streams})")
+        self._first[int(stream)] = True
+
+    # ------------------------------------------------------------------ buffers
+    def _alloc(self, device, Hc: int, Wc: int):
+        n, H, W = self.streams, self.H, self.W
+        with torch.inference_mode(False):  # written in place by later steps, in or out of inference mode
+            def dev(shape, dtype):
+                return torch.empty(shape, dtype=dtype, device=device)
+
+            f32, u8 = torch.float32, torch.uint8
+            fb = [float(f) * float(b) for f, b in zip(self.focal_length_px_model, self.baseline_m)] \
+                if self.depth_enabled else [0.0] * n
+            b = {
+                "disp": dev((n, 1, H, W), f32), "logvar": dev((n, 1, H, W), f32), "state": dev((n, H, W), f32),
+                "depth": dev((n, H, W), f32), "conf": dev((n, H, W), f32), "dcode": dev((n, H, W), u8),
+                "ccode": dev((n, H, W), u8), "edge": dev((n, H, W), u8), "depth_vis": dev((n, Hc, Wc, 3), u8),
+                "conf_vis": dev((n, Hc, Wc, 3), u8), "left_view": dev((n, Hc, Wc, 3), u8),
+                "view": dev((n, Hc, Wc, 3), u8), "center": dev((n, 3), f32),
+                "fb": torch.as_tensor(np.asarray(fb, dtype=np.float32)).to(device),
+                "sel": torch.zeros((n, 8), dtype=f32, device=device),
+                "sel_ws": torch.zeros(L.call("sd_live_select_n_ws_bytes", n) // 4, dtype=torch.int32, device=device),
+                "lut_a": torch.as_tensor(self._lut_host[0]).to(device), "lut_b": torch.as_tensor(self._lut_host[1]).to(device),
+                # numpy frames: a ring of pinned staging buffers [side][stream] (a slot is reused three steps later) and
+                # ONE device copy, in which a held stream's slices keep its previous frame
+                "pin": [torch.empty((2, n, Hc, Wc, 3), dtype=u8, pin_memory=True) for _ in range(3)],
+                "pin_ev": [None, None, None],
+                "frames": dev((2, n, Hc, Wc, 3), u8),
+                "center_host": torch.full((n, 3), float("nan"), dtype=f32, pin_memory=True),
+            }
+            if self.rectification is not None:
+                rects = self.rectification[:1] if self.shared_maps else self.rectification
+                for side in ("l", "r"):
+                    m1s, m2s = [], []
+                    for r in rects:
+                        m1 = np.ascontiguousarray(getattr(r, f"map_{side}_1"))
+                        m2 = np.ascontiguousarray(getattr(r, f"map_{side}_2"))
+                        if m1.shape != (Hc, Wc, 2) or m1.dtype != np.int16 or m2.shape != (Hc, Wc) \
+                                or m2.dtype != np.uint16:
+                            raise ValueError("rectification maps: map1 int16 [Hc, Wc, 2] and map2 uint16 [Hc, Wc] "
+                                             "(cv2.initUndistortRectifyMap(..., cv2.CV_16SC2) or rectify_maps)")
+                        m1s.append(m1)
+                        m2s.append(m2.view(np.int16))
+                    b[f"m1{side}"] = torch.as_tensor(np.stack(m1s)).to(device)
+                    b[f"m2{side}"] = torch.as_tensor(np.stack(m2s)).to(device)
+        self._buf, self._key = b, (device, Hc, Wc)
+        self._first = [True] * n
+        self._seen = [False] * n
+
+    def _frames(self, frames_l, frames_r, fresh, device):
+        """Both sides on the device, uint8 [N, Hc, Wc, 3]. numpy frames: the fresh streams' frames go through pinned
+        staging into the device copy (non_blocking, one copy per side and run of fresh streams)."""
+        n = self.streams
+        if isinstance(frames_l, torch.Tensor) != isinstance(frames_r, torch.Tensor):
+            raise TypeError("both frame sets must be numpy (an array or a sequence of frames) or both device tensors")
+        is_dev = isinstance(frames_l, torch.Tensor)
+        if not is_dev and not isinstance(frames_l, np.ndarray):  # a sequence of N frames
+            if len(frames_l) != n or len(frames_r) != n:
+                raise ValueError(f"expected {n} frames per side, got {len(frames_l)} and {len(frames_r)}")
+            shapes = {tuple(np.shape(f)) for f in list(frames_l) + list(frames_r)}
+            if len(shapes) != 1:
+                raise ValueError(f"frames must be uint8 [Hc, Wc, 3] of one size, got {sorted(shapes)}")
+            shape = (n,) + shapes.pop()
+        else:
+            shape = tuple(frames_l.shape)
+            if tuple(frames_r.shape) != shape:
+                raise ValueError(f"frames must be uint8 [N, Hc, Wc, 3] of one size, got {shape} and "
+                                 f"{tuple(frames_r.shape)}")
+        if len(shape) != 4 or shape[0] != n or shape[3] != 3:
+            raise ValueError(f"frames must be uint8 [N = {n}, Hc, Wc, 3], got {shape}")
+        if self.image_size is not None and (shape[2], shape[1]) != self.image_size:
+            raise RuntimeError(f"Capture size mismatch. Expected calibration size={self.image_size}, "
+                               f"got={(shape[2], shape[1])}.")
+        if self._key != (device, shape[1], shape[2]):
+            self._alloc(device, shape[1], shape[2])
+        held_unseen = [i for i in range(n) if not fresh[i] and not self._seen[i]]
+        if held_unseen:
+            raise ValueError(f"streams {held_unseen} are held (fresh = False) before their first frame: a stream's "
+                             "first step must be fresh")
+        if is_dev:
+            if frames_l.dtype != torch.uint8 or frames_r.dtype != torch.uint8 or frames_l.device != device \
+                    or frames_r.device != device:
+                raise ValueError("device frames must be uint8 tensors on the model's device")
+            return frames_l.contiguous(), frames_r.contiguous()
+        for side in (frames_l, frames_r):
+            if any(f.dtype != np.uint8 for f in ([side] if isinstance(side, np.ndarray) else side)):
+                raise ValueError("frames must be uint8")
+        b = self._buf
+        i = self._stage_i
+        self._stage_i = (i + 1) % 3
+        if b["pin_ev"][i] is not None:
+            b["pin_ev"][i].synchronize()  # the upload of three steps ago: long complete unless frames queue up
+        else:
+            b["pin_ev"][i] = torch.cuda.Event()
+        pin = b["pin"][i].numpy()
+        runs, k = [], 0  # [k0, k1) runs of fresh streams
+        while k < n:
+            if not fresh[k]:
+                k += 1
+                continue
+            k0 = k
+            while k < n and fresh[k]:
+                pin[0, k] = frames_l[k]
+                pin[1, k] = frames_r[k]
+                k += 1
+            runs.append((k0, k))
+        if runs == [(0, n)]:
+            b["frames"].copy_(b["pin"][i], non_blocking=True)
+        else:
+            for k0, k1 in runs:
+                for side in (0, 1):
+                    b["frames"][side, k0:k1].copy_(b["pin"][i][side, k0:k1], non_blocking=True)
+        b["pin_ev"][i].record(torch.cuda.current_stream(device))
+        return b["frames"][0], b["frames"][1]
+
+    # ------------------------------------------------------------------ one step of all streams
+    def step(self, frames_l, frames_r, fresh=None) -> LiveBatchResult:
+        """One frame pair per stream (uint8 BGR [N, Hc, Wc, 3]: numpy arrays, sequences of N numpy [Hc, Wc, 3]
+        frames, or device tensors) through rectification, one batch-N forward and the display stage. fresh: N bools
+        (default: all); a stream that is not fresh is held: with numpy frames its input slot keeps its previous frame
+        (the entry passed for it is ignored), with device tensors the forward reads whatever its slice holds, and in
+        both cases nothing of its results changes. Launches only: no host synchronisation, and no allocation after
+        the first call at a size."""
+        model = self.model
+        if model.training:
+            raise RuntimeError("LiveDepthBatch runs the inference forward: call model.eval()")
+        n = self.streams
+        fresh = [True] * n if fresh is None else [bool(f) for f in fresh]
+        if len(fresh) != n:
+            raise ValueError(f"fresh: one flag per stream ({n}), got {len(fresh)}")
+        eng = model.engine()
+        with torch.cuda.device(eng.device):
+            return self._step(eng, frames_l, frames_r, fresh)
+
+    def _step(self, eng, frames_l, frames_r, fresh) -> LiveBatchResult:
+        n, H, W = self.streams, self.H, self.W
+        fl, fr = self._frames(frames_l, frames_r, fresh, eng.device)
+        b = self._buf
+        Hc, Wc = self._key[1], self._key[2]
+        maps = [L.ptr(b.get(k)) for k in ("m1l", "m2l", "m1r", "m2r")]
+        map_stride = 0 if self.shared_maps else Hc * Wc
+
+        def pack(xin, amax, slot, clear, stream):
+            L.call("sd_live_frontend_n", n, eng.sd_dtype, fl.data_ptr(), fr.data_ptr(), Hc, Wc, *maps, map_stride, H, W,
+                   xin, None, amax, slot, clear, stream)
+
+        eng.pack_weights(cached=True, train=False)
+        eng.forward_packed(H, W, pack, batch=n)
+        unc, on = self.uncertainty, self.depth_enabled
+        logvar = b["logvar"] if unc else None
+        eng.heads(L.SD_HEADS_INFER, disp=b["disp"], logvar=logvar)
+        s = L.stream_handle(eng.device)
+        view = fl
+        if maps[0] is not None:
+            L.call("sd_live_rectify_n", n, fl.data_ptr(), Hc, Wc, maps[0], maps[1], map_stride, b["view"].data_ptr(), s)
+            view = b["view"]
+        a = self.ema_alpha
+        copy = hold = 0
+        for i in range(n):
+            if not fresh[i]:
+                hold |= 1 << i
+                continue
+            if self._first[i] or a <= 0.0:
+                copy |= 1 << i
+            self._first[i] = False
+            self._seen[i] = True
+        f32 = lambda v: float(np.float32(v))  # noqa: E731
+        dlo, dhi = DEPTH_VIS_RANGE_M
+        clo, chi = CONFIDENCE_VIS_RANGE
+        L.call("sd_live_post_n", n, b["disp"].data_ptr(), L.ptr(logvar), H, W, b["state"].data_ptr(), copy, hold, f32(a),
+               f32(1.0 - a), int(on), b["fb"].data_ptr() if on else None, b["depth"].data_ptr() if on else None,
+               b["conf"].data_ptr() if unc else None, b["dcode"].data_ptr() if on else None, f32(dlo),
+               f32(max(dhi - dlo, 1e-6)), b["ccode"].data_ptr() if unc else None, f32(clo), f32(max(chi - clo, 1e-6)), s)
+        if on:
+            L.call("sd_live_contours_n", n, b["depth"].data_ptr(), H, W, f32(dlo), f32(dhi), f32(DEPTH_CONTOUR_STEP_M),
+                   b["edge"].data_ptr(), hold, s)
+        else:  # each stream's disparity in its own 2nd..98th percentile range
+            L.call("sd_live_select_n", n, b["state"].data_ptr(), H, W, b["sel_ws"].data_ptr(), b["sel"].data_ptr(),
+                   b["dcode"].data_ptr(), hold, s)
+        L.call("sd_live_center_n", n, b["state"].data_ptr(), b["depth"].data_ptr() if on else None,
+               b["conf"].data_ptr() if unc else None, H, W, self.center_window, b["center"].data_ptr(), hold, s)
+        L.call("sd_live_compose_n", n, b["dcode"].data_ptr(), b["lut_a"].data_ptr(), b["depth_vis"].data_ptr(),
+               b["ccode"].data_ptr() if unc else None, b["lut_b"].data_ptr() if unc else None,
+               b["conf_vis"].data_ptr() if unc else None, b["edge"].data_ptr() if on else None,
+               view.data_ptr() if on else None, b["left_view"].data_ptr() if on else None, H, W, Hc, Wc, hold, s)
+        return LiveBatchResult(self, disparity=b["state"], logvar=None if logvar is None else logvar[:, 0],
+                               depth_m=b["depth"] if on else None, confidence=b["conf"] if unc else None,
+                               depth_vis=b["depth_vis"], confidence_vis=b["conf_vis"] if unc else None,
+                               left_view=b["left_view"] if on else view)
+
+    def _readout(self) -> np.ndarray:
+        b = self._buf
+        if b is None:
+            raise RuntimeError("readout() before the first step")
+        b["center_host"].copy_(b["center"], non_blocking=True)
+        torch.cuda.current_stream(self._key[0]).synchronize()
+        return b["center_host"].numpy().copy()

@@ -12,6 +12,9 @@
                 forward it wraps (model(x) on a device tensor, events).
 
     python tools/live_bench.py --frames 640x480 --models 320x240,960x720 --precisions fp8,bf16 --json out.json
+
+With --streams 1,2,4,8 it times several camera pairs per step instead (see bench_streams): LiveDepthBatch against N
+LiveDepth objects stepped in turn, and the batched stages, with the shader clock probed before and after each row.
 """
 
 from __future__ import annotations
@@ -168,6 +171,108 @@ def bench_one(precision: str, wm: int, hm: int, wc: int, hc: int, iters: int, wa
     return out
 
 
+def clock_probe(dev, iters: int = 20000) -> float:
+    """Median effective shader clock in MHz under sd_clock_probe's MFMA load (as bench.py reports it)."""
+    n = 256
+    out = torch.zeros(4 * n, dtype=torch.int64, device=dev)
+    sink = torch.zeros(256, dtype=torch.float32, device=dev)
+    L.call("sd_clock_probe", n, iters, out.data_ptr(), sink.data_ptr(), L.stream_handle(dev))
+    torch.cuda.synchronize(dev)
+    o = out.view(n, 4).cpu().double()
+    mhz = ((o[:, 1] - o[:, 0]) / (o[:, 3] - o[:, 2]) * 100.0).sort().values
+    return round(float(mhz[n // 2]), 1)
+
+
+def bench_streams(precision: str, wm: int, hm: int, wc: int, hc: int, iters: int, warmup: int, n: int) -> dict:
+    """n camera pairs per step, on one model:
+      (a) batch : LiveDepthBatch.step + readout (one front end, one batch-n forward, one display stage, one read-out)
+      (b) loop  : n LiveDepth objects sharing the model, each stepped and read out in turn (n batch-1 forwards, n display
+                  stages, n syncing read-outs): what a host with n rigs could do before the batch existed
+      (c) stages: GPU time of the batched stages around the forward for n streams, each alone by events over
+                  back-to-back launches, and their sum for the depth-enabled frame
+    (a) and (b) are timed twice each, alternating, with the shader clock probed before and after."""
+    dev = torch.device("cuda")
+    rng = np.random.default_rng(0)
+    (fl, fr), rect = _scene(rng, wc, hc)
+    fls = np.stack([np.roll(fl, 5 * i, axis=1) for i in range(n)])  # every rig sees its own frames
+    frs = np.stack([np.roll(fr, 5 * i, axis=1) for i in range(n)])
+    torch.manual_seed(0)
+    model = StereoUNet(base_channels=32, precision=precision).to(dev).eval()
+    out = {"precision": precision, "model": f"{wm}x{hm}", "frames": f"{wc}x{hc}", "streams": n,
+           "clock_mhz_before": clock_probe(dev)}
+    with torch.inference_mode():
+        ldb = live.LiveDepthBatch(model, n, (wm, hm), rectification=rect)
+        lds = [live.LiveDepth(model, (wm, hm), rectification=rect) for _ in range(n)]
+
+        def batch_step():
+            ldb.step(fls, frs).readout()
+
+        def loop_step():
+            for i, ld in enumerate(lds):
+                ld.step(fls[i], frs[i]).readout()
+
+        runs = {"batch": [], "loop": []}
+        for _ in range(2):  # alternating: the engine's workspace and graph follow the batch size, so each run warms up
+            for name, fn in (("batch", batch_step), ("loop", loop_step)):
+                runs[name].append(_events(fn, iters, warmup))
+        for name in runs:
+            ev, wall = min(runs[name])
+            out[f"{name}_ms_events"], out[f"{name}_ms_wall"] = ev, wall
+            out[f"{name}_ms_events_runs"] = [r[0] for r in runs[name]]
+            out[f"{name}_frames_per_s"] = n / (wall * 1e-3)
+        batch_step()  # the engine's workspace is the batch's again
+        x = torch.rand(n, 6, hm, wm, device=dev)
+        out["forward_ms_events"] = _events(lambda: model(x, return_uncertainty=True), iters, warmup)[0]
+        batch_step()
+        b, s, eng = ldb._buf, L.stream_handle(dev), model.engine()
+        fld, frd = b["frames"][0], b["frames"][1]
+        maps = [b[k].data_ptr() for k in ("m1l", "m2l", "m1r", "m2r")]
+        xin = eng.ws.t["xin"].data_ptr()
+        p = {k: v.data_ptr() for k, v in b.items() if isinstance(v, torch.Tensor)}
+        stages = {
+            "frontend": lambda: L.call("sd_live_frontend_n", n, eng.sd_dtype, fld.data_ptr(), frd.data_ptr(), hc, wc, *maps,
+                                       0, hm, wm, xin, None, None, 0, -1, s),
+            "rectify_view": lambda: L.call("sd_live_rectify_n", n, fld.data_ptr(), hc, wc, maps[0], maps[1], 0, p["view"],
+                                           s),
+            "post": lambda: L.call("sd_live_post_n", n, p["disp"], p["logvar"], hm, wm, p["state"], (1 << n) - 1, 0, 0.0,
+                                   1.0, 1, p["fb"], p["depth"], p["conf"], p["dcode"], 0.0, 10.0, p["ccode"], 0.0, 5.0, s),
+            "contours": lambda: L.call("sd_live_contours_n", n, p["depth"], hm, wm, 0.0, 10.0, 0.5, p["edge"], 0, s),
+            "select_auto_range": lambda: L.call("sd_live_select_n", n, p["state"], hm, wm, p["sel_ws"], p["sel"],
+                                                p["ccode"], 0, s),
+            "center": lambda: L.call("sd_live_center_n", n, p["state"], p["depth"], p["conf"], hm, wm,
+                                     ldb.center_window, p["center"], 0, s),
+            "compose": lambda: L.call("sd_live_compose_n", n, p["dcode"], p["lut_a"], p["depth_vis"], p["ccode"],
+                                      p["lut_b"], p["conf_vis"], p["edge"], p["view"], p["left_view"], hm, wm, hc, wc, 0, s),
+        }
+        out["stage_us"] = {k: 1e3 * _events(fn, 4 * iters, warmup)[0] for k, fn in stages.items()}
+        used = ("frontend", "rectify_view", "post", "contours", "center", "compose")  # the depth-enabled frame
+        out["stages_ms_sum"] = sum(out["stage_us"][k] for k in used) / 1e3
+    out["clock_mhz_after"] = clock_probe(dev)
+    return out
+
+
+def main_streams(args, wc: int, hc: int) -> None:
+    rows = []
+    for precision in args.precisions.split(","):
+        for m in args.models.split(","):
+            wm, hm = _size(m)
+            for n in (int(v) for v in args.streams.split(",")):
+                row = bench_streams(precision, wm, hm, wc, hc, args.iters, args.warmup, n)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    print("\n| precision | model | N | batch ms/step (events / wall) | batch frames/s | N x LiveDepth ms/step (events / "
+          "wall) | loop frames/s | batch-N forward ms | batched stages ms | clock MHz |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['precision']} | {r['model']} | {r['streams']} | {r['batch_ms_events']:.3f} / {r['batch_ms_wall']:.3f} | "
+              f"{r['batch_frames_per_s']:.0f} | {r['loop_ms_events']:.3f} / {r['loop_ms_wall']:.3f} | "
+              f"{r['loop_frames_per_s']:.0f} | {r['forward_ms_events']:.3f} | {r['stages_ms_sum']:.3f} | "
+              f"{r['clock_mhz_before']:.0f} / {r['clock_mhz_after']:.0f} |")
+    if args.json:
+        args.json.parent.mkdir(parents=True, exist_ok=True)
+        args.json.write_text(json.dumps(rows, indent=1))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--frames", default="640x480")
@@ -177,10 +282,17 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--host-iters", type=int, default=5)
     ap.add_argument("--json", type=Path, default=None)
+    ap.add_argument("--streams", default=None, metavar="N,N,...",
+                    help="e.g. 1,2,4,8: time LiveDepthBatch with N camera pairs per step against N LiveDepth objects "
+                         "stepped in turn, and the batched stages (instead of the single-stream report)")
     args = ap.parse_args()
+    if args.streams and not all(1 <= int(v) <= live.MAX_STREAMS for v in args.streams.split(",")):
+        raise SystemExit(f"--streams: counts in 1..{live.MAX_STREAMS}")
     if not torch.cuda.is_available():
         raise SystemExit("live_bench needs a HIP device: there is no CPU fallback and no CPU timing")
     wc, hc = _size(args.frames)
+    if args.streams:
+        return main_streams(args, wc, hc)
     rows = []
     for precision in args.precisions.split(","):
         for m in args.models.split(","):
