@@ -8,8 +8,8 @@
 // Byte and fp32 streaming kernels, grid-stride (as data.hip): one pixel per thread in the gathering kernels (the front
 // end stores a 16/32-B NHWC vector), four elements per thread with 16-B float and 4-B byte accesses in the plane kernels
 // when counts and pointers allow, else one. No allocation, no synchronisation.
-// Every stage also has a form for n camera pairs per launch (sd_live_*_n, at the end): the same bodies, the stream in
-// blockIdx.y.
+// Every stage is one kernel over n camera pairs, the stream in blockIdx.y, behind one host function; the entry points
+// sd_live_*_n pass their arguments through and the single-stream sd_live_* are their n = 1 case (at the end).
 //
 // Arithmetic: fp32 from the bytes on, every rounding explicit (fmaf, or mul_rn / add_rn / ... under fp contract(off)),
 // so that no contraction choice of the compiler can differ between instantiations: the packed input is bit-identical
@@ -129,8 +129,7 @@ __device__ __forceinline__ void live_px(const uint8_t* __restrict__ img, int Hc,
 
 // one model pixel per thread: 8-channel NHWC vector store [L_R, L_G, L_B, R_R, R_G, R_B, 0, 0], optional NCHW planes,
 // optional max over the frame into amax[slot] with amax[clear] zeroed by the launch's one `clearer` block (the protocol
-// of k_pack_input_amax, misc.hip). Each stage below is written once, as the body of its single-stream kernel and, per
-// stream, of its batched one.
+// of k_pack_input_amax, misc.hip). Each stage below is written once, as the body that its kernel runs per stream.
 template <typename T>
 __device__ __forceinline__ void live_frontend_body(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
                                                    int Hc, int Wc, const short* __restrict__ m1l,
@@ -168,32 +167,21 @@ __device__ __forceinline__ void live_frontend_body(const uint8_t* __restrict__ l
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_live_frontend(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
-                                                       int Hc, int Wc, const short* __restrict__ m1l,
-                                                       const unsigned short* __restrict__ m2l,
-                                                       const short* __restrict__ m1r,
-                                                       const unsigned short* __restrict__ m2r, int H, int W,
-                                                       T* __restrict__ xin, float* __restrict__ nchw, unsigned* amax,
-                                                       int slot, int clear) {
-    live_frontend_body<T>(left, right, Hc, Wc, m1l, m2l, m1r, m2r, H, W, xin, nchw, amax, slot, clear, blockIdx.x == 0);
-}
-
-// The batched kernels: blockIdx.y is the stream, every buffer is [n] of the single-stream layout, and each block runs
-// the single-stream body on its stream's slices (blockIdx.x / gridDim.x keep their meaning inside the body). A stream
-// whose bit is set in `hold` returns before it reads or writes anything. Optional (NULL) buffers stay NULL.
+// The kernels: blockIdx.y is the stream, every buffer is [n] of one stream's layout, and each block runs the body on
+// its stream's slices (blockIdx.x / gridDim.x keep their meaning inside the body). A stream whose bit is set in `hold`
+// returns before it reads or writes anything. Optional (NULL) buffers stay NULL.
 template <typename T> __device__ __forceinline__ T* at(T* p, size_t off) { return p ? p + off : nullptr; }
 __device__ __forceinline__ bool bit(unsigned long long mask, unsigned i) { return (mask >> i) & 1ull; }
 
 // maps: map_stride pixels between the streams' map sets (0: one set for all)
 template <typename T>
-__global__ __launch_bounds__(256) void k_live_frontend_n(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
-                                                         int Hc, int Wc, const short* __restrict__ m1l,
-                                                         const unsigned short* __restrict__ m2l,
-                                                         const short* __restrict__ m1r,
-                                                         const unsigned short* __restrict__ m2r, size_t map_stride, int H,
-                                                         int W, T* __restrict__ xin, float* __restrict__ nchw,
-                                                         unsigned* amax, int slot, int clear) {
+__global__ __launch_bounds__(256) void k_live_frontend(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                                       int Hc, int Wc, const short* __restrict__ m1l,
+                                                       const unsigned short* __restrict__ m2l,
+                                                       const short* __restrict__ m1r,
+                                                       const unsigned short* __restrict__ m2r, size_t map_stride, int H,
+                                                       int W, T* __restrict__ xin, float* __restrict__ nchw,
+                                                       unsigned* amax, int slot, int clear) {
     const size_t i = blockIdx.y, F = (size_t)Hc * Wc * 3, P = (size_t)H * W, mo = i * map_stride;
     live_frontend_body<T>(left + i * F, right + i * F, Hc, Wc, at(m1l, 2 * mo), at(m2l, mo), at(m1r, 2 * mo), at(m2r, mo),
                           H, W, xin + i * P * 8, at(nchw, i * 6 * P), amax, slot, clear,
@@ -215,13 +203,8 @@ __device__ __forceinline__ void live_rectify_body(const uint8_t* __restrict__ im
 }
 __global__ __launch_bounds__(256) void k_live_rectify(const uint8_t* __restrict__ img, int Hc, int Wc,
                                                       const short* __restrict__ map1,
-                                                      const unsigned short* __restrict__ map2, uint8_t* __restrict__ view) {
-    live_rectify_body(img, Hc, Wc, map1, map2, view);
-}
-__global__ __launch_bounds__(256) void k_live_rectify_n(const uint8_t* __restrict__ img, int Hc, int Wc,
-                                                        const short* __restrict__ map1,
-                                                        const unsigned short* __restrict__ map2, size_t map_stride,
-                                                        uint8_t* __restrict__ view) {
+                                                      const unsigned short* __restrict__ map2, size_t map_stride,
+                                                      uint8_t* __restrict__ view) {
     const size_t i = blockIdx.y, F = (size_t)Hc * Wc * 3, mo = i * map_stride;
     live_rectify_body(img + i * F, Hc, Wc, map1 + 2 * mo, map2 + mo, view + i * F);
 }
@@ -275,26 +258,18 @@ __device__ __forceinline__ void live_post_body(const float* __restrict__ pred, c
         }
     }
 }
+// copy: bit i = stream i takes its prediction as is; focal_baseline: fbs[i] per stream, or fb for all when fbs is NULL
 template <int V>
 __global__ __launch_bounds__(256) void k_live_post(const float* __restrict__ pred, const float* __restrict__ logvar, int P,
-                                                   float* __restrict__ state, int copy, float a, float b, int depth_on,
-                                                   float fb, float* __restrict__ depth, float* __restrict__ conf,
-                                                   uint8_t* __restrict__ dcode, float dlo, float dscale,
-                                                   uint8_t* __restrict__ ccode, float clo, float cscale) {
-    live_post_body<V>(pred, logvar, P, state, copy, a, b, depth_on, fb, depth, conf, dcode, dlo, dscale, ccode, clo, cscale);
-}
-// copy: bit i = stream i takes its prediction as is; fbs: focal_baseline per stream (read when depth_on)
-template <int V>
-__global__ __launch_bounds__(256) void k_live_post_n(const float* __restrict__ pred, const float* __restrict__ logvar,
-                                                     int P, float* __restrict__ state, unsigned long long copy,
-                                                     unsigned long long hold, float a, float b, int depth_on,
-                                                     const float* __restrict__ fbs, float* __restrict__ depth,
-                                                     float* __restrict__ conf, uint8_t* __restrict__ dcode, float dlo,
-                                                     float dscale, uint8_t* __restrict__ ccode, float clo, float cscale) {
+                                                   float* __restrict__ state, unsigned long long copy,
+                                                   unsigned long long hold, float a, float b, int depth_on,
+                                                   const float* __restrict__ fbs, float fb, float* __restrict__ depth,
+                                                   float* __restrict__ conf, uint8_t* __restrict__ dcode, float dlo,
+                                                   float dscale, uint8_t* __restrict__ ccode, float clo, float cscale) {
     const unsigned i = blockIdx.y;
     if (bit(hold, i)) return;
     const size_t o = (size_t)i * P;
-    live_post_body<V>(pred + o, at(logvar, o), P, state + o, (int)bit(copy, i), a, b, depth_on, depth_on ? fbs[i] : 0.f,
+    live_post_body<V>(pred + o, at(logvar, o), P, state + o, (int)bit(copy, i), a, b, depth_on, fbs ? fbs[i] : fb,
                       at(depth, o), at(conf, o), at(dcode, o), dlo, dscale, at(ccode, o), clo, cscale);
 }
 
@@ -333,13 +308,7 @@ __device__ __forceinline__ void live_edges_body(const float* __restrict__ depth,
 }
 template <int V>
 __global__ __launch_bounds__(256) void k_live_edges(const float* __restrict__ depth, int H, int W, float dmin, float dmax,
-                                                    float step, uint8_t* __restrict__ edge) {
-    live_edges_body<V>(depth, H, W, dmin, dmax, step, edge);
-}
-template <int V>
-__global__ __launch_bounds__(256) void k_live_edges_n(const float* __restrict__ depth, int H, int W, float dmin,
-                                                      float dmax, float step, uint8_t* __restrict__ edge,
-                                                      unsigned long long hold) {
+                                                    float step, uint8_t* __restrict__ edge, unsigned long long hold) {
     if (bit(hold, blockIdx.y)) return;
     const size_t o = (size_t)blockIdx.y * H * W;
     live_edges_body<V>(depth + o, H, W, dmin, dmax, step, edge + o);
@@ -388,14 +357,10 @@ __device__ __forceinline__ void sel_hist_body(const float* __restrict__ v, int P
     for (int i = threadIdx.x; i < NH * BINS; i += 256)
         if (h[i]) atomicAdd(g + i, h[i]);
 }
-template <int LEVEL>
-__global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ v, int P, unsigned* __restrict__ work) {
-    sel_hist_body<LEVEL>(v, P, work);
-}
 // work [n][SEL_WORDS], sel [n][8]
 template <int LEVEL>
-__global__ __launch_bounds__(256) void k_sel_hist_n(const float* __restrict__ v, int P, unsigned* __restrict__ work,
-                                                    unsigned long long hold) {
+__global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ v, int P, unsigned* __restrict__ work,
+                                                  unsigned long long hold) {
     if (bit(hold, blockIdx.y)) return;
     sel_hist_body<LEVEL>(v + (size_t)blockIdx.y * P, P, work + (size_t)blockIdx.y * SEL_WORDS);
 }
@@ -482,13 +447,9 @@ __device__ __forceinline__ void sel_scan_body(unsigned* __restrict__ work, float
         }
     }
 }
-template <int LEVEL>
-__global__ __launch_bounds__(256) void k_sel_scan(unsigned* __restrict__ work, float* __restrict__ sel) {
-    sel_scan_body<LEVEL>(work, sel);
-}
 template <int LEVEL>  // one block per stream
-__global__ __launch_bounds__(256) void k_sel_scan_n(unsigned* __restrict__ work, float* __restrict__ sel,
-                                                    unsigned long long hold) {
+__global__ __launch_bounds__(256) void k_sel_scan(unsigned* __restrict__ work, float* __restrict__ sel,
+                                                  unsigned long long hold) {
     if (bit(hold, blockIdx.x)) return;
     sel_scan_body<LEVEL>(work + (size_t)blockIdx.x * SEL_WORDS, sel + (size_t)blockIdx.x * 8);
 }
@@ -511,13 +472,7 @@ __device__ __forceinline__ void live_code_auto_body(const float* __restrict__ v,
 }
 template <int V>
 __global__ __launch_bounds__(256) void k_live_code_auto(const float* __restrict__ v, int P, const float* __restrict__ sel,
-                                                        uint8_t* __restrict__ code) {
-    live_code_auto_body<V>(v, P, sel, code);
-}
-template <int V>
-__global__ __launch_bounds__(256) void k_live_code_auto_n(const float* __restrict__ v, int P,
-                                                          const float* __restrict__ sel, uint8_t* __restrict__ code,
-                                                          unsigned long long hold) {
+                                                        uint8_t* __restrict__ code, unsigned long long hold) {
     if (bit(hold, blockIdx.y)) return;
     const size_t o = (size_t)blockIdx.y * P;
     live_code_auto_body<V>(v + o, P, sel + (size_t)blockIdx.y * 8, code + o);
@@ -575,13 +530,9 @@ __device__ __forceinline__ void live_center_body(const float* m0, const float* m
         out[blockIdx.x] = m == 0 ? NAN : (m & 1) ? buf[m / 2] : div_rn(add_rn(buf[m / 2 - 1], buf[m / 2]), 2.f);
     }
 }
-__global__ __launch_bounds__(256) void k_live_center(const float* m0, const float* m1, const float* m2, int H, int W,
-                                                     int window, float* __restrict__ out) {
-    live_center_body(m0, m1, m2, H, W, window, out);
-}
 // grid (3, n): out [n][3]
-__global__ __launch_bounds__(256) void k_live_center_n(const float* m0, const float* m1, const float* m2, int H, int W,
-                                                       int window, float* __restrict__ out, unsigned long long hold) {
+__global__ __launch_bounds__(256) void k_live_center(const float* m0, const float* m1, const float* m2, int H, int W,
+                                                     int window, float* __restrict__ out, unsigned long long hold) {
     if (bit(hold, blockIdx.y)) return;
     const size_t o = (size_t)blockIdx.y * H * W;
     live_center_body(m0 + o, at(m1, o), at(m2, o), H, W, window, out + (size_t)blockIdx.y * 3);
@@ -642,182 +593,185 @@ __device__ __forceinline__ void live_compose_body(const uint8_t* __restrict__ co
         }
     }
 }
+// the colour tables are shared by the streams
 __global__ __launch_bounds__(256) void k_live_compose(const uint8_t* __restrict__ code_a, const uint8_t* __restrict__ lut_a,
                                                       uint8_t* __restrict__ vis_a, const uint8_t* __restrict__ code_b,
                                                       const uint8_t* __restrict__ lut_b, uint8_t* __restrict__ vis_b,
                                                       const uint8_t* __restrict__ edge, const uint8_t* __restrict__ view,
-                                                      uint8_t* __restrict__ left_view, int H, int W, int Hc, int Wc) {
-    live_compose_body(code_a, lut_a, vis_a, code_b, lut_b, vis_b, edge, view, left_view, H, W, Hc, Wc);
-}
-// the colour tables are shared by the streams
-__global__ __launch_bounds__(256) void k_live_compose_n(const uint8_t* __restrict__ code_a, const uint8_t* __restrict__ lut_a,
-                                                        uint8_t* __restrict__ vis_a, const uint8_t* __restrict__ code_b,
-                                                        const uint8_t* __restrict__ lut_b, uint8_t* __restrict__ vis_b,
-                                                        const uint8_t* __restrict__ edge, const uint8_t* __restrict__ view,
-                                                        uint8_t* __restrict__ left_view, int H, int W, int Hc, int Wc,
-                                                        unsigned long long hold) {
+                                                      uint8_t* __restrict__ left_view, int H, int W, int Hc, int Wc,
+                                                      unsigned long long hold) {
     if (bit(hold, blockIdx.y)) return;
     const size_t m = (size_t)blockIdx.y * H * W, f = (size_t)blockIdx.y * Hc * Wc * 3;
     live_compose_body(at(code_a, m), lut_a, at(vis_a, f), at(code_b, m), lut_b, at(vis_b, f), at(edge, m), at(view, f),
                       at(left_view, f), H, W, Hc, Wc);
 }
 
+// ------------------------------------------------------------------ host side
+// One function per stage with all of its checks, the vector-path decision and its launches; fn is the calling entry
+// point's name, for the messages. The vector paths are taken only when every stream's slice is aligned: the element
+// count per stream a multiple of 4 (so that the slices of streams 1..n-1 start on the 16-B / 4-B boundary the base
+// pointer has) and the base pointers aligned.
 bool live_dims_ok(int H, int W) { return H > 0 && W > 0 && (long long)H * W <= INT_MAX / 16; }
+bool streams_ok(int n) { return n >= 1 && n <= 64; }
+bool mask_ok(unsigned long long mask, int n) { return n >= 64 || (mask >> n) == 0ull; }
 
-}  // namespace
+#define LIVE_N_REQUIRE(fn, n) SD_REQUIRE(streams_ok(n), "%s: n = %d streams (1..64)", fn, n)
+#define LIVE_MASK_REQUIRE(fn, name, mask, n) \
+    SD_REQUIRE(mask_ok(mask, n), "%s: " name " 0x%llx has a bit at or above n = %d", fn, (unsigned long long)(mask), n)
+#define LIVE_STRIDE_REQUIRE(fn, map_stride, Hc, Wc)                      \
+    SD_REQUIRE(map_stride == 0 || map_stride == (long long)(Hc) * (Wc), \
+               "%s: map_stride %lld (0: shared maps, Hc * Wc: one set per stream)", fn, map_stride)
 
-extern "C" int sd_live_frontend(int dtype, const uint8_t* left, const uint8_t* right, int Hc, int Wc,
-                                const int16_t* map1_l, const uint16_t* map2_l, const int16_t* map1_r,
-                                const uint16_t* map2_r, int H, int W, void* xin, float* nchw, unsigned* amax, int slot,
-                                int clear, sd_stream s) {
-    SD_REQUIRE(left && right && xin, "sd_live_frontend: null pointer");
-    SD_REQUIRE(live_dims_ok(Hc, Wc) && live_dims_ok(H, W), "sd_live_frontend: bad sizes %dx%d -> %dx%d", Hc, Wc, H, W);
-    SD_REQUIRE(!map1_l == !map2_l && !map1_r == !map2_r, "sd_live_frontend: map1 and map2 go together");
-    SD_REQUIRE(dtype == SD_F32 || dtype == SD_BF16, "sd_live_frontend: dtype %d", dtype);
-    SD_REQUIRE((uintptr_t)xin % 16 == 0, "sd_live_frontend: xin must be 16-B aligned");
-    SD_REQUIRE(!amax || (slot >= 0 && clear != slot), "sd_live_frontend: amax slot %d clear %d", slot, clear);
-    const dim3 g(live_grid((long long)H * W));
+int live_frontend(const char* fn, int n, int dtype, const uint8_t* left, const uint8_t* right, int Hc, int Wc,
+                  const int16_t* map1_l, const uint16_t* map2_l, const int16_t* map1_r, const uint16_t* map2_r,
+                  long long map_stride, int H, int W, void* xin, float* nchw, unsigned* amax, int slot, int clear,
+                  sd_stream s) {
+    LIVE_N_REQUIRE(fn, n);
+    SD_REQUIRE(left && right && xin, "%s: null pointer (left, right, xin)", fn);
+    SD_REQUIRE(live_dims_ok(Hc, Wc) && live_dims_ok(H, W), "%s: bad sizes %dx%d -> %dx%d", fn, Hc, Wc, H, W);
+    SD_REQUIRE(!map1_l == !map2_l && !map1_r == !map2_r, "%s: map1 and map2 go together", fn);
+    LIVE_STRIDE_REQUIRE(fn, map_stride, Hc, Wc);
+    SD_REQUIRE(dtype == SD_F32 || dtype == SD_BF16, "%s: dtype %d", fn, dtype);
+    SD_REQUIRE((uintptr_t)xin % 16 == 0, "%s: xin must be 16-B aligned", fn);
+    SD_REQUIRE(!amax || (slot >= 0 && clear != slot), "%s: amax slot %d clear %d", fn, slot, clear);
+    const dim3 g(live_grid((long long)H * W), n);
     if (dtype == SD_BF16)
         hipLaunchKernelGGL(k_live_frontend<__bf16>, g, dim3(256), 0, to_stream(s), left, right, Hc, Wc, map1_l, map2_l,
-                           map1_r, map2_r, H, W, (__bf16*)xin, nchw, amax, slot, clear);
+                           map1_r, map2_r, (size_t)map_stride, H, W, (__bf16*)xin, nchw, amax, slot, clear);
     else
         hipLaunchKernelGGL(k_live_frontend<float>, g, dim3(256), 0, to_stream(s), left, right, Hc, Wc, map1_l, map2_l,
-                           map1_r, map2_r, H, W, (float*)xin, nchw, amax, slot, clear);
-    return sd_check_launch("sd_live_frontend");
+                           map1_r, map2_r, (size_t)map_stride, H, W, (float*)xin, nchw, amax, slot, clear);
+    return sd_check_launch(fn);
 }
 
-extern "C" int sd_live_rectify(const uint8_t* frame, int Hc, int Wc, const int16_t* map1, const uint16_t* map2,
-                               uint8_t* view, sd_stream s) {
-    SD_REQUIRE(frame && view && map1 && map2, "sd_live_rectify: null pointer");
-    SD_REQUIRE(live_dims_ok(Hc, Wc), "sd_live_rectify: bad sizes %dx%d", Hc, Wc);
-    hipLaunchKernelGGL(k_live_rectify, dim3(live_grid((long long)Hc * Wc)), dim3(256), 0, to_stream(s), frame, Hc, Wc,
-                       map1, map2, view);
-    return sd_check_launch("sd_live_rectify");
+int live_rectify(const char* fn, int n, const uint8_t* frames, int Hc, int Wc, const int16_t* map1, const uint16_t* map2,
+                 long long map_stride, uint8_t* views, sd_stream s) {
+    LIVE_N_REQUIRE(fn, n);
+    SD_REQUIRE(frames && views, "%s: null pointer (frames, views)", fn);
+    SD_REQUIRE(map1 && map2, "%s: null pointer (map1 and map2 go together, both needed)", fn);
+    SD_REQUIRE(live_dims_ok(Hc, Wc), "%s: bad sizes %dx%d", fn, Hc, Wc);
+    LIVE_STRIDE_REQUIRE(fn, map_stride, Hc, Wc);
+    hipLaunchKernelGGL(k_live_rectify, dim3(live_grid((long long)Hc * Wc), n), dim3(256), 0, to_stream(s), frames, Hc, Wc,
+                       map1, map2, (size_t)map_stride, views);
+    return sd_check_launch(fn);
 }
 
-extern "C" int sd_live_post(const float* disp, const float* logvar, int H, int W, float* state, int copy, float alpha,
-                            float one_minus_alpha, int depth_on, float focal_baseline, float* depth, float* conf,
-                            uint8_t* depth_code, float depth_lo, float depth_scale, uint8_t* conf_code, float conf_lo,
-                            float conf_scale, sd_stream s) {
-    SD_REQUIRE(disp && state, "sd_live_post: null pointer");
-    SD_REQUIRE(live_dims_ok(H, W), "sd_live_post: bad sizes %dx%d", H, W);
-    SD_REQUIRE(!depth_on || depth, "sd_live_post: depth enabled without a depth buffer");
-    SD_REQUIRE(!logvar || conf, "sd_live_post: logvar without a confidence buffer");
-    SD_REQUIRE((!depth_code || depth_scale > 0.f) && (!conf_code || conf_scale > 0.f), "sd_live_post: code scale <= 0");
+// focal_baseline: the device array fbs [n] when fb_array (sd_live_post_n), else the scalar fb for every stream
+int live_post(const char* fn, int n, const float* disp, const float* logvar, int H, int W, float* state,
+              unsigned long long copy_mask, unsigned long long hold_mask, float alpha, float one_minus_alpha, int depth_on,
+              bool fb_array, const float* fbs, float fb, float* depth, float* conf, uint8_t* depth_code, float depth_lo,
+              float depth_scale, uint8_t* conf_code, float conf_lo, float conf_scale, sd_stream s) {
+    LIVE_N_REQUIRE(fn, n);
+    SD_REQUIRE(disp && state, "%s: null pointer (disp, state)", fn);
+    SD_REQUIRE(live_dims_ok(H, W), "%s: bad sizes %dx%d", fn, H, W);
+    LIVE_MASK_REQUIRE(fn, "copy_mask", copy_mask, n);
+    LIVE_MASK_REQUIRE(fn, "hold_mask", hold_mask, n);
+    SD_REQUIRE(!depth_on || (depth && (fbs || !fb_array)),
+               "%s: depth enabled without a depth buffer or focal_baseline", fn);
+    SD_REQUIRE(!logvar || conf, "%s: logvar without a confidence buffer", fn);
+    SD_REQUIRE((!depth_code || depth_scale > 0.f) && (!conf_code || conf_scale > 0.f), "%s: code scale <= 0", fn);
     const int P = H * W;
     const bool vec = P % 4 == 0 && aligned(disp, 16) && aligned(logvar, 16) && aligned(state, 16) && aligned(depth, 16) &&
                      aligned(conf, 16) && aligned(depth_code, 4) && aligned(conf_code, 4);
-    hipLaunchKernelGGL(vec ? k_live_post<4> : k_live_post<1>, dim3(live_grid(vec ? P / 4 : P)), dim3(256), 0, to_stream(s),
-                       disp, logvar, P, state, copy, alpha, one_minus_alpha, depth_on, focal_baseline, depth, conf,
-                       depth_code, depth_lo, depth_scale, conf_code, conf_lo, conf_scale);
-    return sd_check_launch("sd_live_post");
+    hipLaunchKernelGGL(vec ? k_live_post<4> : k_live_post<1>, dim3(live_grid(vec ? P / 4 : P), n), dim3(256), 0,
+                       to_stream(s), disp, logvar, P, state, copy_mask, hold_mask, alpha, one_minus_alpha, depth_on,
+                       depth_on && fb_array ? fbs : nullptr, fb, depth, conf, depth_code, depth_lo, depth_scale, conf_code,
+                       conf_lo, conf_scale);
+    return sd_check_launch(fn);
 }
 
-extern "C" int sd_live_contours(const float* depth, int H, int W, float min_depth, float max_depth, float step,
-                                uint8_t* edge, sd_stream s) {
-    SD_REQUIRE(depth && edge, "sd_live_contours: null pointer");
-    SD_REQUIRE(live_dims_ok(H, W), "sd_live_contours: bad sizes %dx%d", H, W);
-    SD_REQUIRE(step > 0.f && max_depth > min_depth, "sd_live_contours: bad range");
+int live_contours(const char* fn, int n, const float* depth, int H, int W, float min_depth, float max_depth, float step,
+                  uint8_t* edge, unsigned long long hold_mask, sd_stream s) {
+    LIVE_N_REQUIRE(fn, n);
+    SD_REQUIRE(depth && edge, "%s: null pointer (depth, edge)", fn);
+    SD_REQUIRE(live_dims_ok(H, W), "%s: bad sizes %dx%d", fn, H, W);
+    LIVE_MASK_REQUIRE(fn, "hold_mask", hold_mask, n);
+    SD_REQUIRE(step > 0.f && max_depth > min_depth, "%s: bad range", fn);
+    // W % 4 == 0 makes H * W a multiple of 4 too: every stream's slice keeps the base pointers' alignment
     const bool vec = W % 4 == 0 && aligned(depth, 16) && aligned(edge, 4);
-    hipLaunchKernelGGL(vec ? k_live_edges<4> : k_live_edges<1>, dim3(live_grid((long long)H * W / (vec ? 4 : 1))), dim3(256),
-                       0, to_stream(s), depth, H, W, min_depth, max_depth, step, edge);
-    return sd_check_launch("sd_live_contours");
+    hipLaunchKernelGGL(vec ? k_live_edges<4> : k_live_edges<1>, dim3(live_grid((long long)H * W / (vec ? 4 : 1)), n),
+                       dim3(256), 0, to_stream(s), depth, H, W, min_depth, max_depth, step, edge, hold_mask);
+    return sd_check_launch(fn);
 }
 
-extern "C" long long sd_live_select_ws_bytes(void) { return (long long)SEL_WORDS * 4; }
-
-extern "C" int sd_live_select(const float* values, int H, int W, unsigned* work, float* sel, uint8_t* code,
-                              sd_stream s) {
-    SD_REQUIRE(values && work && sel, "sd_live_select: null pointer");
-    SD_REQUIRE(live_dims_ok(H, W), "sd_live_select: bad sizes %dx%d", H, W);
+int live_select(const char* fn, int n, const float* values, int H, int W, unsigned* work, float* sel, uint8_t* code,
+                unsigned long long hold_mask, sd_stream s) {
+    LIVE_N_REQUIRE(fn, n);
+    SD_REQUIRE(values && work && sel, "%s: null pointer (values, work, sel)", fn);
+    SD_REQUIRE(live_dims_ok(H, W), "%s: bad sizes %dx%d", fn, H, W);
+    LIVE_MASK_REQUIRE(fn, "hold_mask", hold_mask, n);
     const int P = H * W;
-    const dim3 g(cdiv(P, 1024) < 256 ? cdiv(P, 1024) : 256), b(256);
+    const dim3 g(cdiv(P, 1024) < 256 ? cdiv(P, 1024) : 256, n), g1(n), b(256);
     hipStream_t st = to_stream(s);
-    hipLaunchKernelGGL(k_sel_hist<1>, g, b, 0, st, values, P, work);
-    hipLaunchKernelGGL(k_sel_scan<1>, dim3(1), b, 0, st, work, sel);
-    hipLaunchKernelGGL(k_sel_hist<2>, g, b, 0, st, values, P, work);
-    hipLaunchKernelGGL(k_sel_scan<2>, dim3(1), b, 0, st, work, sel);
-    hipLaunchKernelGGL(k_sel_hist<3>, g, b, 0, st, values, P, work);
-    hipLaunchKernelGGL(k_sel_scan<3>, dim3(1), b, 0, st, work, sel);
+    hipLaunchKernelGGL(k_sel_hist<1>, g, b, 0, st, values, P, work, hold_mask);
+    hipLaunchKernelGGL(k_sel_scan<1>, g1, b, 0, st, work, sel, hold_mask);
+    hipLaunchKernelGGL(k_sel_hist<2>, g, b, 0, st, values, P, work, hold_mask);
+    hipLaunchKernelGGL(k_sel_scan<2>, g1, b, 0, st, work, sel, hold_mask);
+    hipLaunchKernelGGL(k_sel_hist<3>, g, b, 0, st, values, P, work, hold_mask);
+    hipLaunchKernelGGL(k_sel_scan<3>, g1, b, 0, st, work, sel, hold_mask);
     if (code) {
         const bool vec = P % 4 == 0 && aligned(values, 16) && aligned(code, 4);
-        hipLaunchKernelGGL(vec ? k_live_code_auto<4> : k_live_code_auto<1>, dim3(live_grid(vec ? P / 4 : P)), b, 0, st,
-                           values, P, sel, code);
+        hipLaunchKernelGGL(vec ? k_live_code_auto<4> : k_live_code_auto<1>, dim3(live_grid(vec ? P / 4 : P), n), b, 0, st,
+                           values, P, sel, code, hold_mask);
     }
-    return sd_check_launch("sd_live_select");
+    return sd_check_launch(fn);
 }
 
-extern "C" int sd_live_center(const float* disp, const float* depth, const float* conf, int H, int W, int window,
-                              float* out3, sd_stream s) {
-    SD_REQUIRE(disp && out3, "sd_live_center: null pointer");
-    SD_REQUIRE(live_dims_ok(H, W), "sd_live_center: bad sizes %dx%d", H, W);
-    SD_REQUIRE(window >= 0 && window <= 63, "sd_live_center: window %d (max 63)", window);
-    hipLaunchKernelGGL(k_live_center, dim3(3), dim3(256), 0, to_stream(s), disp, depth, conf, H, W, window, out3);
-    return sd_check_launch("sd_live_center");
+int live_center(const char* fn, int n, const float* disp, const float* depth, const float* conf, int H, int W, int window,
+                float* out3, unsigned long long hold_mask, sd_stream s) {
+    LIVE_N_REQUIRE(fn, n);
+    SD_REQUIRE(disp && out3, "%s: null pointer (disp, out3)", fn);
+    SD_REQUIRE(live_dims_ok(H, W), "%s: bad sizes %dx%d", fn, H, W);
+    LIVE_MASK_REQUIRE(fn, "hold_mask", hold_mask, n);
+    SD_REQUIRE(window >= 0 && window <= 63, "%s: window %d (max 63)", fn, window);
+    hipLaunchKernelGGL(k_live_center, dim3(3, n), dim3(256), 0, to_stream(s), disp, depth, conf, H, W, window, out3,
+                       hold_mask);
+    return sd_check_launch(fn);
 }
 
-extern "C" int sd_live_compose(const uint8_t* code_a, const uint8_t* lut_a, uint8_t* vis_a, const uint8_t* code_b,
-                               const uint8_t* lut_b, uint8_t* vis_b, const uint8_t* edge, const uint8_t* view,
-                               uint8_t* left_view, int H, int W, int Hc, int Wc, sd_stream s) {
-    SD_REQUIRE(code_a || code_b || left_view, "sd_live_compose: nothing to do");
-    SD_REQUIRE(!code_a || (lut_a && vis_a), "sd_live_compose: null pointer (image a)");
-    SD_REQUIRE(!code_b || (lut_b && vis_b), "sd_live_compose: null pointer (image b)");
-    SD_REQUIRE(!left_view || view, "sd_live_compose: null pointer (view)");
-    SD_REQUIRE(!edge || left_view, "sd_live_compose: contour mask without a left view to paint");
-    SD_REQUIRE(live_dims_ok(H, W) && live_dims_ok(Hc, Wc), "sd_live_compose: bad sizes %dx%d -> %dx%d", H, W, Hc, Wc);
-    hipLaunchKernelGGL(k_live_compose, dim3(live_grid((long long)Hc * Wc)), dim3(256), 0, to_stream(s), code_a, lut_a, vis_a,
-                       code_b, lut_b, vis_b, edge, view, left_view, H, W, Hc, Wc);
-    return sd_check_launch("sd_live_compose");
+int live_compose(const char* fn, int n, const uint8_t* code_a, const uint8_t* lut_a, uint8_t* vis_a, const uint8_t* code_b,
+                 const uint8_t* lut_b, uint8_t* vis_b, const uint8_t* edge, const uint8_t* view, uint8_t* left_view, int H,
+                 int W, int Hc, int Wc, unsigned long long hold_mask, sd_stream s) {
+    LIVE_N_REQUIRE(fn, n);
+    SD_REQUIRE(code_a || code_b || left_view, "%s: nothing to do", fn);
+    SD_REQUIRE(!code_a || (lut_a && vis_a), "%s: null pointer (image a: lut_a, vis_a)", fn);
+    SD_REQUIRE(!code_b || (lut_b && vis_b), "%s: null pointer (image b: lut_b, vis_b)", fn);
+    SD_REQUIRE(!left_view || view, "%s: null pointer (view)", fn);
+    SD_REQUIRE(!edge || left_view, "%s: contour mask without a left view to paint", fn);
+    SD_REQUIRE(live_dims_ok(H, W) && live_dims_ok(Hc, Wc), "%s: bad sizes %dx%d -> %dx%d", fn, H, W, Hc, Wc);
+    LIVE_MASK_REQUIRE(fn, "hold_mask", hold_mask, n);
+    hipLaunchKernelGGL(k_live_compose, dim3(live_grid((long long)Hc * Wc), n), dim3(256), 0, to_stream(s), code_a, lut_a,
+                       vis_a, code_b, lut_b, vis_b, edge, view, left_view, H, W, Hc, Wc, hold_mask);
+    return sd_check_launch(fn);
 }
 
-// ------------------------------------------------------------------ several streams per launch
-// The same stages for n camera pairs: every buffer is [n] of the single-stream layout, blockIdx.y is the stream, and
-// each entry point issues the launches its single-stream form issues for one. The vector paths are taken only when
-// every stream's slice is aligned: the element count per stream a multiple of 4 (so that the slices of streams
-// 1..n-1 start on the 16-B / 4-B boundary the base pointer has) and the base pointers aligned.
-namespace {
-bool streams_ok(int n) { return n >= 1 && n <= 64; }
-bool mask_ok(unsigned long long mask, int n) { return n >= 64 || (mask >> n) == 0ull; }
 }  // namespace
 
-#define LIVE_N_REQUIRE(fn, n) SD_REQUIRE(streams_ok(n), fn ": n = %d streams (1..64)", n)
-#define LIVE_MASK_REQUIRE(fn, name, mask, n) \
-    SD_REQUIRE(mask_ok(mask, n), fn ": " name " 0x%llx has a bit at or above n = %d", (unsigned long long)(mask), n)
-
+// ------------------------------------------------------------------ entry points
+// sd_live_X_n hands its arguments to live_X; sd_live_X is the same call for one stream: n = 1, no stream held, shared
+// maps (map_stride 0), `copy` as bit 0 of the copy mask, focal_baseline by value.
 extern "C" int sd_live_frontend_n(int n, int dtype, const uint8_t* left, const uint8_t* right, int Hc, int Wc,
                                   const int16_t* map1_l, const uint16_t* map2_l, const int16_t* map1_r,
                                   const uint16_t* map2_r, long long map_stride, int H, int W, void* xin, float* nchw,
                                   unsigned* amax, int slot, int clear, sd_stream s) {
-    LIVE_N_REQUIRE("sd_live_frontend_n", n);
-    SD_REQUIRE(left && right && xin, "sd_live_frontend_n: null pointer (left, right, xin)");
-    SD_REQUIRE(live_dims_ok(Hc, Wc) && live_dims_ok(H, W), "sd_live_frontend_n: bad sizes %dx%d -> %dx%d", Hc, Wc, H, W);
-    SD_REQUIRE(!map1_l == !map2_l && !map1_r == !map2_r, "sd_live_frontend_n: map1 and map2 go together");
-    SD_REQUIRE(map_stride == 0 || map_stride == (long long)Hc * Wc,
-               "sd_live_frontend_n: map_stride %lld (0: shared maps, Hc * Wc: one set per stream)", map_stride);
-    SD_REQUIRE(dtype == SD_F32 || dtype == SD_BF16, "sd_live_frontend_n: dtype %d", dtype);
-    SD_REQUIRE((uintptr_t)xin % 16 == 0, "sd_live_frontend_n: xin must be 16-B aligned");
-    SD_REQUIRE(!amax || (slot >= 0 && clear != slot), "sd_live_frontend_n: amax slot %d clear %d", slot, clear);
-    const dim3 g(live_grid((long long)H * W), n);
-    if (dtype == SD_BF16)
-        hipLaunchKernelGGL(k_live_frontend_n<__bf16>, g, dim3(256), 0, to_stream(s), left, right, Hc, Wc, map1_l, map2_l,
-                           map1_r, map2_r, (size_t)map_stride, H, W, (__bf16*)xin, nchw, amax, slot, clear);
-    else
-        hipLaunchKernelGGL(k_live_frontend_n<float>, g, dim3(256), 0, to_stream(s), left, right, Hc, Wc, map1_l, map2_l,
-                           map1_r, map2_r, (size_t)map_stride, H, W, (float*)xin, nchw, amax, slot, clear);
-    return sd_check_launch("sd_live_frontend_n");
+    return live_frontend("sd_live_frontend_n", n, dtype, left, right, Hc, Wc, map1_l, map2_l, map1_r, map2_r, map_stride, H,
+                         W, xin, nchw, amax, slot, clear, s);
+}
+extern "C" int sd_live_frontend(int dtype, const uint8_t* left, const uint8_t* right, int Hc, int Wc,
+                                const int16_t* map1_l, const uint16_t* map2_l, const int16_t* map1_r,
+                                const uint16_t* map2_r, int H, int W, void* xin, float* nchw, unsigned* amax, int slot,
+                                int clear, sd_stream s) {
+    return live_frontend("sd_live_frontend", 1, dtype, left, right, Hc, Wc, map1_l, map2_l, map1_r, map2_r, 0, H, W, xin,
+                         nchw, amax, slot, clear, s);
 }
 
 extern "C" int sd_live_rectify_n(int n, const uint8_t* frames, int Hc, int Wc, const int16_t* map1, const uint16_t* map2,
                                  long long map_stride, uint8_t* views, sd_stream s) {
-    LIVE_N_REQUIRE("sd_live_rectify_n", n);
-    SD_REQUIRE(frames && views, "sd_live_rectify_n: null pointer (frames, views)");
-    SD_REQUIRE(map1 && map2, "sd_live_rectify_n: null pointer (map1 and map2 go together, both needed)");
-    SD_REQUIRE(live_dims_ok(Hc, Wc), "sd_live_rectify_n: bad sizes %dx%d", Hc, Wc);
-    SD_REQUIRE(map_stride == 0 || map_stride == (long long)Hc * Wc,
-               "sd_live_rectify_n: map_stride %lld (0: shared maps, Hc * Wc: one set per stream)", map_stride);
-    hipLaunchKernelGGL(k_live_rectify_n, dim3(live_grid((long long)Hc * Wc), n), dim3(256), 0, to_stream(s), frames, Hc, Wc,
-                       map1, map2, (size_t)map_stride, views);
-    return sd_check_launch("sd_live_rectify_n");
+    return live_rectify("sd_live_rectify_n", n, frames, Hc, Wc, map1, map2, map_stride, views, s);
+}
+extern "C" int sd_live_rectify(const uint8_t* frame, int Hc, int Wc, const int16_t* map1, const uint16_t* map2,
+                               uint8_t* view, sd_stream s) {
+    return live_rectify("sd_live_rectify", 1, frame, Hc, Wc, map1, map2, 0, view, s);
 }
 
 extern "C" int sd_live_post_n(int n, const float* disp, const float* logvar, int H, int W, float* state,
@@ -825,88 +779,59 @@ extern "C" int sd_live_post_n(int n, const float* disp, const float* logvar, int
                               float one_minus_alpha, int depth_on, const float* focal_baseline, float* depth, float* conf,
                               uint8_t* depth_code, float depth_lo, float depth_scale, uint8_t* conf_code, float conf_lo,
                               float conf_scale, sd_stream s) {
-    LIVE_N_REQUIRE("sd_live_post_n", n);
-    SD_REQUIRE(disp && state, "sd_live_post_n: null pointer (disp, state)");
-    SD_REQUIRE(live_dims_ok(H, W), "sd_live_post_n: bad sizes %dx%d", H, W);
-    LIVE_MASK_REQUIRE("sd_live_post_n", "copy_mask", copy_mask, n);
-    LIVE_MASK_REQUIRE("sd_live_post_n", "hold_mask", hold_mask, n);
-    SD_REQUIRE(!depth_on || (depth && focal_baseline),
-               "sd_live_post_n: depth enabled without a depth buffer or focal_baseline");
-    SD_REQUIRE(!logvar || conf, "sd_live_post_n: logvar without a confidence buffer");
-    SD_REQUIRE((!depth_code || depth_scale > 0.f) && (!conf_code || conf_scale > 0.f), "sd_live_post_n: code scale <= 0");
-    const int P = H * W;
-    const bool vec = P % 4 == 0 && aligned(disp, 16) && aligned(logvar, 16) && aligned(state, 16) && aligned(depth, 16) &&
-                     aligned(conf, 16) && aligned(depth_code, 4) && aligned(conf_code, 4);
-    hipLaunchKernelGGL(vec ? k_live_post_n<4> : k_live_post_n<1>, dim3(live_grid(vec ? P / 4 : P), n), dim3(256), 0,
-                       to_stream(s), disp, logvar, P, state, copy_mask, hold_mask, alpha, one_minus_alpha, depth_on,
-                       focal_baseline, depth, conf, depth_code, depth_lo, depth_scale, conf_code, conf_lo, conf_scale);
-    return sd_check_launch("sd_live_post_n");
+    return live_post("sd_live_post_n", n, disp, logvar, H, W, state, copy_mask, hold_mask, alpha, one_minus_alpha, depth_on,
+                     true, focal_baseline, 0.f, depth, conf, depth_code, depth_lo, depth_scale, conf_code, conf_lo,
+                     conf_scale, s);
+}
+extern "C" int sd_live_post(const float* disp, const float* logvar, int H, int W, float* state, int copy, float alpha,
+                            float one_minus_alpha, int depth_on, float focal_baseline, float* depth, float* conf,
+                            uint8_t* depth_code, float depth_lo, float depth_scale, uint8_t* conf_code, float conf_lo,
+                            float conf_scale, sd_stream s) {
+    return live_post("sd_live_post", 1, disp, logvar, H, W, state, copy ? 1 : 0, 0, alpha, one_minus_alpha, depth_on, false,
+                     nullptr, focal_baseline, depth, conf, depth_code, depth_lo, depth_scale, conf_code, conf_lo,
+                     conf_scale, s);
 }
 
 extern "C" int sd_live_contours_n(int n, const float* depth, int H, int W, float min_depth, float max_depth, float step,
                                   uint8_t* edge, unsigned long long hold_mask, sd_stream s) {
-    LIVE_N_REQUIRE("sd_live_contours_n", n);
-    SD_REQUIRE(depth && edge, "sd_live_contours_n: null pointer (depth, edge)");
-    SD_REQUIRE(live_dims_ok(H, W), "sd_live_contours_n: bad sizes %dx%d", H, W);
-    LIVE_MASK_REQUIRE("sd_live_contours_n", "hold_mask", hold_mask, n);
-    SD_REQUIRE(step > 0.f && max_depth > min_depth, "sd_live_contours_n: bad range");
-    // W % 4 == 0 makes H * W a multiple of 4 too: every stream's slice keeps the base pointers' alignment
-    const bool vec = W % 4 == 0 && aligned(depth, 16) && aligned(edge, 4);
-    hipLaunchKernelGGL(vec ? k_live_edges_n<4> : k_live_edges_n<1>, dim3(live_grid((long long)H * W / (vec ? 4 : 1)), n),
-                       dim3(256), 0, to_stream(s), depth, H, W, min_depth, max_depth, step, edge, hold_mask);
-    return sd_check_launch("sd_live_contours_n");
+    return live_contours("sd_live_contours_n", n, depth, H, W, min_depth, max_depth, step, edge, hold_mask, s);
+}
+extern "C" int sd_live_contours(const float* depth, int H, int W, float min_depth, float max_depth, float step,
+                                uint8_t* edge, sd_stream s) {
+    return live_contours("sd_live_contours", 1, depth, H, W, min_depth, max_depth, step, edge, 0, s);
 }
 
 extern "C" long long sd_live_select_n_ws_bytes(int n) { return streams_ok(n) ? (long long)n * SEL_WORDS * 4 : -1; }
+extern "C" long long sd_live_select_ws_bytes(void) { return sd_live_select_n_ws_bytes(1); }
 
 extern "C" int sd_live_select_n(int n, const float* values, int H, int W, unsigned* work, float* sel, uint8_t* code,
                                 unsigned long long hold_mask, sd_stream s) {
-    LIVE_N_REQUIRE("sd_live_select_n", n);
-    SD_REQUIRE(values && work && sel, "sd_live_select_n: null pointer (values, work, sel)");
-    SD_REQUIRE(live_dims_ok(H, W), "sd_live_select_n: bad sizes %dx%d", H, W);
-    LIVE_MASK_REQUIRE("sd_live_select_n", "hold_mask", hold_mask, n);
-    const int P = H * W;
-    const dim3 g(cdiv(P, 1024) < 256 ? cdiv(P, 1024) : 256, n), g1(n), b(256);
-    hipStream_t st = to_stream(s);
-    hipLaunchKernelGGL(k_sel_hist_n<1>, g, b, 0, st, values, P, work, hold_mask);
-    hipLaunchKernelGGL(k_sel_scan_n<1>, g1, b, 0, st, work, sel, hold_mask);
-    hipLaunchKernelGGL(k_sel_hist_n<2>, g, b, 0, st, values, P, work, hold_mask);
-    hipLaunchKernelGGL(k_sel_scan_n<2>, g1, b, 0, st, work, sel, hold_mask);
-    hipLaunchKernelGGL(k_sel_hist_n<3>, g, b, 0, st, values, P, work, hold_mask);
-    hipLaunchKernelGGL(k_sel_scan_n<3>, g1, b, 0, st, work, sel, hold_mask);
-    if (code) {
-        const bool vec = P % 4 == 0 && aligned(values, 16) && aligned(code, 4);
-        hipLaunchKernelGGL(vec ? k_live_code_auto_n<4> : k_live_code_auto_n<1>, dim3(live_grid(vec ? P / 4 : P), n), b, 0, st,
-                           values, P, sel, code, hold_mask);
-    }
-    return sd_check_launch("sd_live_select_n");
+    return live_select("sd_live_select_n", n, values, H, W, work, sel, code, hold_mask, s);
+}
+extern "C" int sd_live_select(const float* values, int H, int W, unsigned* work, float* sel, uint8_t* code,
+                              sd_stream s) {
+    return live_select("sd_live_select", 1, values, H, W, work, sel, code, 0, s);
 }
 
 extern "C" int sd_live_center_n(int n, const float* disp, const float* depth, const float* conf, int H, int W, int window,
                                 float* out3, unsigned long long hold_mask, sd_stream s) {
-    LIVE_N_REQUIRE("sd_live_center_n", n);
-    SD_REQUIRE(disp && out3, "sd_live_center_n: null pointer (disp, out3)");
-    SD_REQUIRE(live_dims_ok(H, W), "sd_live_center_n: bad sizes %dx%d", H, W);
-    LIVE_MASK_REQUIRE("sd_live_center_n", "hold_mask", hold_mask, n);
-    SD_REQUIRE(window >= 0 && window <= 63, "sd_live_center_n: window %d (max 63)", window);
-    hipLaunchKernelGGL(k_live_center_n, dim3(3, n), dim3(256), 0, to_stream(s), disp, depth, conf, H, W, window, out3,
-                       hold_mask);
-    return sd_check_launch("sd_live_center_n");
+    return live_center("sd_live_center_n", n, disp, depth, conf, H, W, window, out3, hold_mask, s);
+}
+extern "C" int sd_live_center(const float* disp, const float* depth, const float* conf, int H, int W, int window,
+                              float* out3, sd_stream s) {
+    return live_center("sd_live_center", 1, disp, depth, conf, H, W, window, out3, 0, s);
 }
 
 extern "C" int sd_live_compose_n(int n, const uint8_t* code_a, const uint8_t* lut_a, uint8_t* vis_a, const uint8_t* code_b,
                                  const uint8_t* lut_b, uint8_t* vis_b, const uint8_t* edge, const uint8_t* view,
                                  uint8_t* left_view, int H, int W, int Hc, int Wc, unsigned long long hold_mask,
                                  sd_stream s) {
-    LIVE_N_REQUIRE("sd_live_compose_n", n);
-    SD_REQUIRE(code_a || code_b || left_view, "sd_live_compose_n: nothing to do");
-    SD_REQUIRE(!code_a || (lut_a && vis_a), "sd_live_compose_n: null pointer (image a: lut_a, vis_a)");
-    SD_REQUIRE(!code_b || (lut_b && vis_b), "sd_live_compose_n: null pointer (image b: lut_b, vis_b)");
-    SD_REQUIRE(!left_view || view, "sd_live_compose_n: null pointer (view)");
-    SD_REQUIRE(!edge || left_view, "sd_live_compose_n: contour mask without a left view to paint");
-    SD_REQUIRE(live_dims_ok(H, W) && live_dims_ok(Hc, Wc), "sd_live_compose_n: bad sizes %dx%d -> %dx%d", H, W, Hc, Wc);
-    LIVE_MASK_REQUIRE("sd_live_compose_n", "hold_mask", hold_mask, n);
-    hipLaunchKernelGGL(k_live_compose_n, dim3(live_grid((long long)Hc * Wc), n), dim3(256), 0, to_stream(s), code_a, lut_a,
-                       vis_a, code_b, lut_b, vis_b, edge, view, left_view, H, W, Hc, Wc, hold_mask);
-    return sd_check_launch("sd_live_compose_n");
+    return live_compose("sd_live_compose_n", n, code_a, lut_a, vis_a, code_b, lut_b, vis_b, edge, view, left_view, H, W, Hc,
+                        Wc, hold_mask, s);
+}
+extern "C" int sd_live_compose(const uint8_t* code_a, const uint8_t* lut_a, uint8_t* vis_a, const uint8_t* code_b,
+                               const uint8_t* lut_b, uint8_t* vis_b, const uint8_t* edge, const uint8_t* view,
+                               uint8_t* left_view, int H, int W, int Hc, int Wc, sd_stream s) {
+    return live_compose("sd_live_compose", 1, code_a, lut_a, vis_a, code_b, lut_b, vis_b, edge, view, left_view, H, W, Hc,
+                        Wc, 0, s);
 }

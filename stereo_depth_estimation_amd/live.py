@@ -169,8 +169,13 @@ def load_calibration(path, rectify: bool = True) -> Calibration:
 
 
 # ---------------------------------------------------------------------- the device path
+# LiveDepthBatch is the implementation, for N rigs per step; LiveDepth (at the end) is its N = 1 case for one rig.
+MAX_STREAMS = 64
+
+
 class LiveResult:
-    """Device tensors of one step (views of LiveDepth's buffers: the next step overwrites them). depth_m,
+    """Device tensors of one step (views of the live object's buffers: the next step overwrites them, except the
+    slices of streams it holds): stream-major [N, ...] from LiveDepthBatch, stream 0's from LiveDepth. depth_m,
     confidence and confidence_vis are None when depth / uncertainty is off."""
 
     __slots__ = ("disparity", "logvar", "depth_m", "confidence", "depth_vis", "confidence_vis", "left_view", "_live")
@@ -180,218 +185,14 @@ class LiveResult:
         for k, v in kw.items():
             setattr(self, k, v)
 
-    def readout(self) -> tuple[float, float, float]:
-        """(center_disparity, center_depth_m, center_confidence) of the latest step: one 12-byte copy and the only
-        host synchronisation of the frame path."""
+    def readout(self):
+        """(center_disparity, center_depth_m, center_confidence) of the latest step: float32 [N, 3] from LiveDepthBatch
+        (a held stream's row is its last fresh frame's), a tuple of three floats from LiveDepth. One 12 * N-byte copy
+        and the only host synchronisation of the frame path."""
         return self._live._readout()
 
 
-class LiveDepth:
-    def __init__(self, model, model_size=(320, 240), rectification=None, focal_length_px=None, baseline_m=None,
-                 calibration_width_px=None, uncertainty=True, colormap="turbo", ema_alpha=0.0, center_window=15):
-        """model: an eval-mode StereoUNet (in_channels 6) on a HIP device. model_size = (width, height).
-        rectification: an object with the reference's RectificationData attributes (map_l_1, map_l_2, map_r_1,
-        map_r_2, image_size, focal_length_px, baseline_m); when given it defines the geometry (depth_live_dl.py:
-        407-410). Depth is on when a baseline and a focal length scaled to the model width exist (:412-423).
-        colormap: a name of COLORMAP_NAMES or a [256, 3] uint8 BGR table."""
-        if not 0.0 <= float(ema_alpha) <= 1.0:
-            raise ValueError("ema_alpha must be in [0, 1]")
-        if not 0 <= int(center_window) <= MAX_CENTER_WINDOW:
-            raise ValueError(f"center_window must be in [0, {MAX_CENTER_WINDOW}]")
-        if model.in_channels != 6:
-            raise ValueError("LiveDepth needs a stereo model (in_channels 6)")
-        self.model = model
-        self.W, self.H = int(model_size[0]), int(model_size[1])
-        if self.H % 16 or self.W % 16 or self.H <= 0 or self.W <= 0:
-            raise ValueError("model_size must be positive multiples of 16 (four 2x2 pools)")
-        self.rectification = rectification
-        if rectification is not None:
-            focal_length_px = rectification.focal_length_px
-            baseline_m = rectification.baseline_m
-            calibration_width_px = rectification.image_size[0]
-        focal_model = None
-        if focal_length_px is not None and calibration_width_px is not None and calibration_width_px > 0:
-            focal_model = focal_length_px * (self.W / float(calibration_width_px))
-        self.depth_enabled = baseline_m is not None and focal_model is not None
-        self.focal_length_px_model, self.baseline_m = focal_model, baseline_m
-        self.uncertainty = bool(uncertainty)
-        self.ema_alpha = float(ema_alpha)
-        self.center_window = int(center_window)
-        lut = colormap_lut(colormap) if isinstance(colormap, str) else np.asarray(colormap)
-        if lut.shape != (256, 3) or lut.dtype != np.uint8:
-            raise ValueError("colormap: a name or a [256, 3] uint8 BGR table")
-        self._lut_host = (np.ascontiguousarray(lut), colormap_lut(CONFIDENCE_COLORMAP))
-        self._first = True
-        self._buf = None  # device buffers of one (device, capture size)
-        self._key = None
-        self._stage_i = 0
-
-    def reset(self) -> None:
-        """Forget the EMA state: the next frame's prediction is taken as is."""
-        self._first = True
-
-    # ------------------------------------------------------------------ buffers
-    def _alloc(self, device, Hc: int, Wc: int):
-        H, W = self.H, self.W
-        with torch.inference_mode(False):  # written in place by later steps, in or out of inference mode
-            def dev(shape, dtype):
-                return torch.empty(shape, dtype=dtype, device=device)
-
-            b = {
-                "disp": dev((1, 1, H, W), torch.float32), "logvar": dev((1, 1, H, W), torch.float32),
-                "state": dev((H, W), torch.float32), "depth": dev((H, W), torch.float32),
-                "conf": dev((H, W), torch.float32), "dcode": dev((H, W), torch.uint8), "ccode": dev((H, W), torch.uint8),
-                "edge": dev((H, W), torch.uint8), "depth_vis": dev((Hc, Wc, 3), torch.uint8),
-                "conf_vis": dev((Hc, Wc, 3), torch.uint8), "left_view": dev((Hc, Wc, 3), torch.uint8),
-                "view": dev((Hc, Wc, 3), torch.uint8), "center": dev((3,), torch.float32),
-                "sel": torch.zeros(8, dtype=torch.float32, device=device),
-                "sel_ws": torch.zeros(L.call("sd_live_select_ws_bytes") // 4, dtype=torch.int32, device=device),
-                "lut_a": torch.as_tensor(self._lut_host[0]).to(device), "lut_b": torch.as_tensor(self._lut_host[1]).to(device),
-                # numpy frames: a ring of pinned staging pairs (a slot is reused three steps later)
-                "pin": [torch.empty((2, Hc, Wc, 3), dtype=torch.uint8, pin_memory=True) for _ in range(3)],
-                "pin_ev": [None, None, None],
-                "frames": [dev((2, Hc, Wc, 3), torch.uint8) for _ in range(3)],
-                "center_host": torch.full((3,), float("nan"), dtype=torch.float32, pin_memory=True),
-            }
-            r = self.rectification
-            if r is not None:
-                for side in ("l", "r"):
-                    m1 = np.ascontiguousarray(getattr(r, f"map_{side}_1"))
-                    m2 = np.ascontiguousarray(getattr(r, f"map_{side}_2"))
-                    if m1.shape != (Hc, Wc, 2) or m1.dtype != np.int16 or m2.shape != (Hc, Wc) or m2.dtype != np.uint16:
-                        raise ValueError("rectification maps: map1 int16 [Hc, Wc, 2] and map2 uint16 [Hc, Wc] "
-                                         "(cv2.initUndistortRectifyMap(..., cv2.CV_16SC2) or rectify_maps)")
-                    b[f"m1{side}"] = torch.as_tensor(m1).to(device)
-                    b[f"m2{side}"] = torch.as_tensor(m2.view(np.int16)).to(device)
-        self._buf, self._key = b, (device, Hc, Wc)
-        self._first = True
-
-    def _frames(self, frame_l, frame_r, device):
-        """Both frames on the device, uint8 [Hc, Wc, 3]. numpy frames: pinned staging, non_blocking copies."""
-        if isinstance(frame_l, torch.Tensor) != isinstance(frame_r, torch.Tensor):
-            raise TypeError("both frames must be numpy arrays or both device tensors")
-        shape = tuple(frame_l.shape)
-        if len(shape) != 3 or shape[2] != 3 or tuple(frame_r.shape) != shape:
-            raise ValueError(f"frames must be uint8 [Hc, Wc, 3] of one size, got {shape} and {tuple(frame_r.shape)}")
-        r = self.rectification
-        if r is not None and (shape[1], shape[0]) != tuple(r.image_size):
-            raise RuntimeError(f"Capture size mismatch. Expected calibration size={tuple(r.image_size)}, "
-                               f"got={(shape[1], shape[0])}.")
-        if self._key != (device, shape[0], shape[1]):
-            self._alloc(device, shape[0], shape[1])
-        if isinstance(frame_l, torch.Tensor):
-            if frame_l.dtype != torch.uint8 or frame_r.dtype != torch.uint8 or frame_l.device != device \
-                    or frame_r.device != device:
-                raise ValueError("device frames must be uint8 tensors on the model's device")
-            return frame_l.contiguous(), frame_r.contiguous()
-        if frame_l.dtype != np.uint8 or frame_r.dtype != np.uint8:
-            raise ValueError("frames must be uint8")
-        b = self._buf
-        i = self._stage_i
-        self._stage_i = (i + 1) % 3
-        if b["pin_ev"][i] is not None:
-            b["pin_ev"][i].synchronize()  # the upload of three steps ago: long complete unless frames queue up
-        else:
-            b["pin_ev"][i] = torch.cuda.Event()
-        pin = b["pin"][i].numpy()
-        pin[0] = frame_l
-        pin[1] = frame_r
-        b["frames"][i].copy_(b["pin"][i], non_blocking=True)
-        b["pin_ev"][i].record(torch.cuda.current_stream(device))
-        return b["frames"][i][0], b["frames"][i][1]
-
-    # ------------------------------------------------------------------ one frame
-    def step(self, frame_l, frame_r) -> LiveResult:
-        """One frame pair (uint8 BGR [Hc, Wc, 3], numpy or device tensors) through rectification, the model and the
-        display stage. Launches only: no host synchronisation, and no allocation after the first call at a size."""
-        model = self.model
-        if model.training:
-            raise RuntimeError("LiveDepth runs the inference forward: call model.eval()")
-        eng = model.engine()
-        with torch.cuda.device(eng.device):
-            return self._step(eng, frame_l, frame_r)
-
-    def _step(self, eng, frame_l, frame_r) -> LiveResult:
-        H, W = self.H, self.W
-        fl, fr = self._frames(frame_l, frame_r, eng.device)
-        b = self._buf
-        Hc, Wc = self._key[1], self._key[2]
-        maps = [L.ptr(b.get(k)) for k in ("m1l", "m2l", "m1r", "m2r")]
-
-        def pack(xin, amax, slot, clear, stream):
-            L.call("sd_live_frontend", eng.sd_dtype, fl.data_ptr(), fr.data_ptr(), Hc, Wc, *maps, H, W, xin, None, amax,
-                   slot, clear, stream)
-
-        eng.pack_weights(cached=True, train=False)
-        eng.forward_packed(H, W, pack)
-        logvar = b["logvar"] if self.uncertainty else None
-        eng.heads(L.SD_HEADS_INFER, disp=b["disp"], logvar=logvar)
-        s = L.stream_handle(eng.device)
-        view = fl
-        if maps[0] is not None:
-            L.call("sd_live_rectify", fl.data_ptr(), Hc, Wc, maps[0], maps[1], b["view"].data_ptr(), s)
-            view = b["view"]
-        a = self.ema_alpha
-        copy = int(self._first or a <= 0.0)
-        self._first = False
-        on = self.depth_enabled
-        fb = float(np.float32(float(self.focal_length_px_model) * float(self.baseline_m))) if on else 0.0
-        dlo, dhi = DEPTH_VIS_RANGE_M
-        clo, chi = CONFIDENCE_VIS_RANGE
-        L.call("sd_live_post", b["disp"].data_ptr(), L.ptr(logvar), H, W, b["state"].data_ptr(), copy,
-               float(np.float32(a)), float(np.float32(1.0 - a)), int(on), fb, b["depth"].data_ptr() if on else None,
-               b["conf"].data_ptr() if self.uncertainty else None, b["dcode"].data_ptr() if on else None,
-               float(np.float32(dlo)), float(np.float32(max(dhi - dlo, 1e-6))),
-               b["ccode"].data_ptr() if self.uncertainty else None, float(np.float32(clo)),
-               float(np.float32(max(chi - clo, 1e-6))), s)
-        if on:
-            L.call("sd_live_contours", b["depth"].data_ptr(), H, W, float(np.float32(dlo)), float(np.float32(dhi)),
-                   float(np.float32(DEPTH_CONTOUR_STEP_M)), b["edge"].data_ptr(), s)
-        else:  # the disparity in its own 2nd..98th percentile range
-            L.call("sd_live_select", b["state"].data_ptr(), H, W, b["sel_ws"].data_ptr(), b["sel"].data_ptr(),
-                   b["dcode"].data_ptr(), s)
-        L.call("sd_live_center", b["state"].data_ptr(), b["depth"].data_ptr() if on else None,
-               b["conf"].data_ptr() if self.uncertainty else None, H, W, self.center_window, b["center"].data_ptr(), s)
-        unc = self.uncertainty
-        L.call("sd_live_compose", b["dcode"].data_ptr(), b["lut_a"].data_ptr(), b["depth_vis"].data_ptr(),
-               b["ccode"].data_ptr() if unc else None, b["lut_b"].data_ptr() if unc else None,
-               b["conf_vis"].data_ptr() if unc else None, b["edge"].data_ptr() if on else None,
-               view.data_ptr() if on else None, b["left_view"].data_ptr() if on else None, H, W, Hc, Wc, s)
-        return LiveResult(self, disparity=b["state"], logvar=None if logvar is None else logvar[0, 0],
-                          depth_m=b["depth"] if on else None, confidence=b["conf"] if unc else None,
-                          depth_vis=b["depth_vis"], confidence_vis=b["conf_vis"] if unc else None,
-                          left_view=b["left_view"] if on else view)
-
-    def _readout(self) -> tuple[float, float, float]:
-        b = self._buf
-        if b is None:
-            raise RuntimeError("readout() before the first step")
-        b["center_host"].copy_(b["center"], non_blocking=True)
-        torch.cuda.current_stream(self._key[0]).synchronize()
-        c = b["center_host"]
-        return float(c[0]), float(c[1]), float(c[2])
-
-
-# ---------------------------------------------------------------------- several rigs per step
-MAX_STREAMS = 64
-
-
-class LiveBatchResult:
-    """Device tensors of one LiveDepthBatch step, stream-major (views of its buffers: the next step overwrites them,
-    except the slices of streams it holds). depth_m, confidence and confidence_vis are None when depth / uncertainty
-    is off."""
-
-    __slots__ = ("disparity", "logvar", "depth_m", "confidence", "depth_vis", "confidence_vis", "left_view", "_live")
-
-    def __init__(self, live, **kw):
-        self._live = live
-        for k, v in kw.items():
-            setattr(self, k, v)
-
-    def readout(self) -> np.ndarray:
-        """float32 [N, 3]: (center_disparity, center_depth_m, center_confidence) per stream as of the latest step
-        (a held stream's row is its last fresh frame's). One 12 * N-byte copy and the only host synchronisation."""
-        return self._live._readout()
+LiveBatchResult = LiveResult
 
 
 def _per_stream(value, streams: int, name: str) -> list:
@@ -404,7 +205,7 @@ def _per_stream(value, streams: int, name: str) -> list:
 
 
 class LiveDepthBatch:
-    """LiveDepth for `streams` camera pairs of one capture size and one model: one front-end launch, one batch-N
+    """The frame path for `streams` camera pairs of one capture size and one model: one front-end launch, one batch-N
     forward and one launch sequence of the display stage per step, whatever N is.
 
         live = LiveDepthBatch(model, streams=4, model_size=(960, 720), rectification=[rect0, rect1, rect2, rect3])
@@ -417,10 +218,13 @@ class LiveDepthBatch:
 
     def __init__(self, model, streams, model_size=(320, 240), rectification=None, focal_length_px=None, baseline_m=None,
                  calibration_width_px=None, uncertainty=True, colormap="turbo", ema_alpha=0.0, center_window=15):
-        """streams: 1..64. rectification: None, one RectificationData-like object shared by all streams, or a sequence
-        of one per stream (all of one image_size); focal_length_px, baseline_m, calibration_width_px: scalars or
-        sequences of one per stream. Depth is enabled per stream by LiveDepth's rule, and must be enabled for all
-        streams or for none. Everything else as LiveDepth."""
+        """model: an eval-mode StereoUNet (in_channels 6) on a HIP device. streams: 1..64. model_size = (width,
+        height). rectification: None, one object with the reference's RectificationData attributes (map_l_1, map_l_2,
+        map_r_1, map_r_2, image_size, focal_length_px, baseline_m) shared by all streams, or a sequence of one per
+        stream (all of one image_size); when given it defines the geometry (depth_live_dl.py:407-410).
+        focal_length_px, baseline_m, calibration_width_px: scalars or sequences of one per stream. Depth is on for a
+        stream when a baseline and a focal length scaled to the model width exist (:412-423), and must be on for all
+        streams or for none. colormap: a name of COLORMAP_NAMES or a [256, 3] uint8 BGR table."""
         n = int(streams)
         if not 1 <= n <= MAX_STREAMS:
             raise ValueError(f"streams must be in [1, {MAX_STREAMS}]")
@@ -429,7 +233,7 @@ class LiveDepthBatch:
         if not 0 <= int(center_window) <= MAX_CENTER_WINDOW:
             raise ValueError(f"center_window must be in [0, {MAX_CENTER_WINDOW}]")
         if model.in_channels != 6:
-            raise ValueError("LiveDepthBatch needs a stereo model (in_channels 6)")
+            raise ValueError("LiveDepth / LiveDepthBatch need a stereo model (in_channels 6)")
         self.model = model
         self.streams = n
         self.W, self.H = int(model_size[0]), int(model_size[1])
@@ -593,16 +397,17 @@ class LiveDepthBatch:
         return b["frames"][0], b["frames"][1]
 
     # ------------------------------------------------------------------ one step of all streams
-    def step(self, frames_l, frames_r, fresh=None) -> LiveBatchResult:
+    def step(self, frames_l, frames_r, fresh=None) -> LiveResult:
         """One frame pair per stream (uint8 BGR [N, Hc, Wc, 3]: numpy arrays, sequences of N numpy [Hc, Wc, 3]
         frames, or device tensors) through rectification, one batch-N forward and the display stage. fresh: N bools
         (default: all); a stream that is not fresh is held: with numpy frames its input slot keeps its previous frame
         (the entry passed for it is ignored), with device tensors the forward reads whatever its slice holds, and in
         both cases nothing of its results changes. Launches only: no host synchronisation, and no allocation after
-        the first call at a size."""
+        the first call at a size. Like the results, the device copy of numpy frames is overwritten by the next step
+        (stream-ordered after this step's kernels)."""
         model = self.model
         if model.training:
-            raise RuntimeError("LiveDepthBatch runs the inference forward: call model.eval()")
+            raise RuntimeError("LiveDepth / LiveDepthBatch run the inference forward: call model.eval()")
         n = self.streams
         fresh = [True] * n if fresh is None else [bool(f) for f in fresh]
         if len(fresh) != n:
@@ -611,7 +416,7 @@ class LiveDepthBatch:
         with torch.cuda.device(eng.device):
             return self._step(eng, frames_l, frames_r, fresh)
 
-    def _step(self, eng, frames_l, frames_r, fresh) -> LiveBatchResult:
+    def _step(self, eng, frames_l, frames_r, fresh) -> LiveResult:
         n, H, W = self.streams, self.H, self.W
         fl, fr = self._frames(frames_l, frames_r, fresh, eng.device)
         b = self._buf
@@ -662,10 +467,10 @@ class LiveDepthBatch:
                b["ccode"].data_ptr() if unc else None, b["lut_b"].data_ptr() if unc else None,
                b["conf_vis"].data_ptr() if unc else None, b["edge"].data_ptr() if on else None,
                view.data_ptr() if on else None, b["left_view"].data_ptr() if on else None, H, W, Hc, Wc, hold, s)
-        return LiveBatchResult(self, disparity=b["state"], logvar=None if logvar is None else logvar[:, 0],
-                               depth_m=b["depth"] if on else None, confidence=b["conf"] if unc else None,
-                               depth_vis=b["depth_vis"], confidence_vis=b["conf_vis"] if unc else None,
-                               left_view=b["left_view"] if on else view)
+        return LiveResult(self, disparity=b["state"], logvar=None if logvar is None else logvar[:, 0],
+                          depth_m=b["depth"] if on else None, confidence=b["conf"] if unc else None,
+                          depth_vis=b["depth_vis"], confidence_vis=b["conf_vis"] if unc else None,
+                          left_view=b["left_view"] if on else view)
 
     def _readout(self) -> np.ndarray:
         b = self._buf
@@ -674,3 +479,48 @@ class LiveDepthBatch:
         b["center_host"].copy_(b["center"], non_blocking=True)
         torch.cuda.current_stream(self._key[0]).synchronize()
         return b["center_host"].numpy().copy()
+
+
+# ---------------------------------------------------------------------- one rig
+def _of_batch(name):
+    return property(lambda self: getattr(self._batch, name), lambda self, value: setattr(self._batch, name, value))
+
+
+class LiveDepth:
+    """One camera pair: LiveDepthBatch with one stream, taking [Hc, Wc, 3] frames and handing out stream 0's tensors
+    and a tuple of three floats (see the module docstring)."""
+
+    def __init__(self, model, model_size=(320, 240), rectification=None, focal_length_px=None, baseline_m=None,
+                 calibration_width_px=None, uncertainty=True, colormap="turbo", ema_alpha=0.0, center_window=15):
+        """As LiveDepthBatch, with one rectification object (or None) and scalar geometry."""
+        self._batch = LiveDepthBatch(model, 1, model_size, rectification, focal_length_px, baseline_m,
+                                     calibration_width_px, uncertainty, colormap, ema_alpha, center_window)
+        self.rectification = rectification
+
+    model, W, H = _of_batch("model"), _of_batch("W"), _of_batch("H")
+    depth_enabled, uncertainty = _of_batch("depth_enabled"), _of_batch("uncertainty")
+    ema_alpha, center_window = _of_batch("ema_alpha"), _of_batch("center_window")
+    focal_length_px_model = property(lambda self: self._batch.focal_length_px_model[0])
+    baseline_m = property(lambda self: self._batch.baseline_m[0])
+
+    def reset(self) -> None:
+        """Forget the EMA state: the next frame's prediction is taken as is."""
+        self._batch.reset()
+
+    def step(self, frame_l, frame_r) -> LiveResult:
+        """One frame pair (uint8 BGR [Hc, Wc, 3], numpy or device tensors) through rectification, the model and the
+        display stage. Launches only: no host synchronisation, and no allocation after the first call at a size.
+        The next step overwrites the results and the device copy of numpy frames."""
+        fl, fr = frame_l[None], frame_r[None]
+        res = self._batch.step(fl, fr)
+        out = LiveResult(self)
+        for k in LiveResult.__slots__[:-1]:
+            v = getattr(res, k)
+            setattr(out, k, None if v is None else v[0])
+        if res.left_view is fl:  # device frames shown as they came: the caller's own tensor
+            out.left_view = frame_l
+        return out
+
+    def _readout(self) -> tuple[float, float, float]:
+        c = self._batch._readout()[0]
+        return float(c[0]), float(c[1]), float(c[2])

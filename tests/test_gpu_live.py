@@ -427,7 +427,7 @@ def test_step_without_depth_uses_the_auto_range_and_device_frames():
         c = res.readout()
     assert np.isnan(c[1]) and np.isnan(c[2]) and c[0] > 0
     disp = res.disparity.cpu().numpy()
-    got = ld._buf["sel"].cpu().numpy()[5:7]
+    got = ld._batch._buf["sel"][0].cpu().numpy()[5:7]
     assert _ulp_diff(got, _percentiles64(disp)) <= 1
     want_vis = R.compose(R.codes(disp, got[0], got[1]), lut, Hc, Wc)
     assert np.abs(res.depth_vis.cpu().numpy().astype(int) - want_vis.astype(int)).max() <= 1

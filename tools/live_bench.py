@@ -107,9 +107,9 @@ def bench_one(precision: str, wm: int, hm: int, wc: int, hc: int, iters: int, wa
         # ---- the forward alone, and each new stage alone (GPU time, events)
         x = torch.rand(1, 6, hm, wm, device=dev)
         out["forward_ms_events"] = _events(lambda: model(x, return_uncertainty=True), iters, warmup)[0]
-        b, s = ld._buf, L.stream_handle(dev)
+        b, s = ld._batch._buf, L.stream_handle(dev)  # [1] of every buffer: stream 0's slice starts at the base pointer
         eng = model.engine()
-        fld, frd = b["frames"][0][0], b["frames"][0][1]
+        fld, frd = b["frames"][0], b["frames"][1]
         maps = [b[k].data_ptr() for k in ("m1l", "m2l", "m1r", "m2r")]
         xin = eng.ws.t["xin"].data_ptr()
         f32 = lambda v: float(np.float32(v))  # noqa: E731
