@@ -571,6 +571,36 @@ int sd_sgm_post(const int16_t* q, int H, int W, const double* Q, float* disp, fl
  * value counts (sd_live_center keeps only finite, > 0 values); none: NaN. window <= 63. */
 int sd_sgm_center(const float* z, int H, int W, int window, float* out, sd_stream s);
 
+/* ---- several stereo rigs (n streams, 1 <= n <= 64) through one matcher step ----
+ * The stream is a grid dimension of the kernels above: every entry point below issues the launches its single-stream
+ * form issues for one stream, each covering all n streams, and stream i's bytes are identical to the single-stream
+ * entry point run on stream i's slices. All streams share one size and one matcher configuration. Buffers are
+ * stream-major: gray_l, gray_r u8 [n][H][W]; q int16 [n][H][W]; disp, z f32 [n][H][W]; code u8 [n][H][W] (H * W
+ * need not be a multiple of anything). Workspaces are n slices of the single-stream layout. Arguments are checked
+ * before any launch (n first); no allocation, no synchronisation, graph-capturable.
+ * Gray has no batched entry: a u8 [n][H][W][3] buffer is sd_sgm_gray on n * H rows (sd_sgm_gray(bgr, n * H, W, gray, s)).
+ * Rectification and the colour image are sd_live_rectify_n (shared or per-stream maps through map_stride) and
+ * sd_live_compose_n (hold_mask 0). */
+/* n * sd_sgm_ws_bytes(H, W, D), slice i at i * sd_sgm_ws_bytes (a multiple of 256); negative for n outside 1..64.
+ * 640 x 480, D = 128: n * 160 MB. Host only. */
+long long sd_sgm_ws_bytes_n(int n, int H, int W, int D);
+/* sd_sgm_compute_mode for n streams; work: sd_sgm_ws_bytes_n, 256-B aligned. SD_SGM_MODE_3WAY with n = 1 issues exactly
+ * sd_sgm_compute's launches. */
+int sd_sgm_compute_n(int n, const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
+                     int num_disparities, int block_size, int P1, int P2, int disp12_max_diff, int uniqueness_ratio,
+                     int speckle_window, int speckle_range, int pre_filter_cap, int mode, void* work, int16_t* q,
+                     sd_stream s);
+/* sd_sgm_speckle on q [n][H][W]: components never join across a stream boundary (parent links are indices local to
+ * the stream). work: n slices of sd_sgm_speckle_ws_bytes(H, W). */
+int sd_sgm_speckle_n(int n, int16_t* q, int H, int W, int invalid_value, int window, int range, void* work,
+                     sd_stream s);
+/* sd_sgm_post per stream. Qdev: a DEVICE array f64 [n][16], one row-major 4 x 4 matrix per stream; minmax: u32 [n][2],
+ * each stream's display range is its own. */
+int sd_sgm_post_n(int n, const int16_t* q, int H, int W, const double* Qdev, float* disp, float* z, uint8_t* code,
+                  unsigned* minmax, sd_stream s);
+/* sd_sgm_center per stream: z f32 [n][H][W] -> out f32 [n], one block per stream. */
+int sd_sgm_center_n(int n, const float* z, int H, int W, int window, float* out, sd_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,12 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_sgm_compute_mode": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sd_sgm_post": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "sd_sgm_center": (_i, [_p, _i, _i, _i, _p, _p]),
+    # the matcher for n streams: n first
+    "sd_sgm_ws_bytes_n": (ctypes.c_longlong, [_i, _i, _i, _i]),
+    "sd_sgm_compute_n": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "sd_sgm_speckle_n": (_i, [_i, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "sd_sgm_post_n": (_i, [_i, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "sd_sgm_center_n": (_i, [_i, _p, _i, _i, _i, _p, _p]),
 }
 
 _lib = None
@@ -257,7 +263,7 @@ def kernel_name(name: str, *args) -> str:
 def call(name: str, *args) -> int:
     """Call an int-returning entry point; raise StereoHipError with sd_last_error() on failure."""
     lib = load()
-    if name.endswith(("_rows", "_splits", "_ok", "_bytes")) or name == "sd_version":
+    if name.endswith(("_rows", "_splits", "_ok", "_bytes", "_bytes_n")) or name == "sd_version":
         return getattr(lib, name)(*args)
     if _hook is not None:
         _hook(name, args, "pre")

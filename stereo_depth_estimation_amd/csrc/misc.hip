@@ -23,7 +23,7 @@ int sd_check_launch(const char* what) {
     return SD_OK;
 }
 
-extern "C" int sd_version(void) { return 103; }
+extern "C" int sd_version(void) { return 104; }
 extern "C" const char* sd_last_error(void) { return g_err; }
 extern "C" int sd_device_init(int device) {
     if (hipSetDevice(device) != hipSuccess) return sd_check_launch("sd_device_init");

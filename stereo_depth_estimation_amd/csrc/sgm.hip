@@ -12,6 +12,8 @@
 //                      of k_sgm_walk each (S += L); tests/sgm_modes_ref.py restates them
 //   speckle          : union-find over the 4-neighbour graph (atomicMin on parent links), count at the roots, invalidate
 //   post             : disparity, fp64 reprojection, min/max on the device, display codes; the centre nanmedian
+// Several stereo rigs of one size go through the same launches (sd_sgm_compute_n / _speckle_n / _post_n / _center_n):
+// the stream is a grid dimension of these kernels, and the single-stream entry points are their n = 1 case.
 // No allocation, no synchronisation: every entry point is graph-capturable. Workspace is the caller's.
 #include <limits.h>
 #include <math.h>
@@ -65,6 +67,25 @@ const char* sgm_params_error(const SgmParams& p) {
     return nullptr;
 }
 
+// Several streams (stereo rigs) in one launch: the stream is a grid dimension (y, or z where y is taken) and every
+// buffer is n slices of the single-stream layout. A kernel folds stream * (elements per slice) into its base pointers
+// once, before any loop, from a wave-uniform index: the scan loops keep their instruction count. The fold sits behind
+// a branch that stream 0, and so every block of a single-stream launch, skips: the 64-bit scalar multiplies are not
+// free in the streaming kernels, where every wave of a CU runs its few instructions at once on one scalar unit.
+__device__ __forceinline__ unsigned stream_index(unsigned block) {
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)block);
+}
+// first statement of `if (stream_index(..))`: an empty side effect, so that the body stays behind a branch
+__device__ __forceinline__ void stream_branch() { asm volatile(""); }
+template <class P> __device__ __forceinline__ void seek_stream(P& p, unsigned sid, long long stride) {  // P: a pointer
+    p += (size_t)sid * (size_t)stride;
+}
+// the scan kernels (one long-lived wave per scan line) fold it without the branch: their prologue is a rounding error
+// of their run time, and their main loops compile to what they were
+__device__ __forceinline__ size_t stream_off(unsigned block, long long stride) {
+    return (size_t)stream_index(block) * (size_t)stride;
+}
+
 // ------------------------------------------------------------------ stages 1, 2
 __global__ __launch_bounds__(256) void k_sgm_gray(const uint8_t* __restrict__ bgr, int P, uint8_t* __restrict__ g) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < P; i += gridDim.x * 256) {
@@ -74,8 +95,13 @@ __global__ __launch_bounds__(256) void k_sgm_gray(const uint8_t* __restrict__ bg
 }
 
 __global__ __launch_bounds__(256) void k_sgm_prefilter(const uint8_t* __restrict__ a, int H, int W, int cap,
-                                                       uint8_t* __restrict__ out) {
+                                                       uint8_t* __restrict__ out, long long a_stride,
+                                                       long long out_stride) {
     const int P = H * W;
+    if (const unsigned sid = stream_index(blockIdx.y)) {
+        stream_branch();
+        seek_stream(a, sid, a_stride), seek_stream(out, sid, out_stride);
+    }
     for (int i = blockIdx.x * 256 + threadIdx.x; i < P; i += gridDim.x * 256) {
         const int y = i / W, x = i - y * W;
         const int xm = max(x - 1, 0), xp = min(x + 1, W - 1);
@@ -110,7 +136,9 @@ __device__ __forceinline__ int bt_plane(const uint8_t* __restrict__ a, const uin
 // (private to the thread: no barrier), their sum in a register. Lanes run along d: 2-byte stores, 128 B per wave.
 __global__ __launch_bounds__(256) void k_sgm_cost_rows(const uint8_t* __restrict__ gl, const uint8_t* __restrict__ gr,
                                                        const uint8_t* __restrict__ pl, const uint8_t* __restrict__ pr,
-                                                       int W, int minD, int D, int bs, uint16_t* __restrict__ Hs) {
+                                                       int W, int minD, int D, int bs, uint16_t* __restrict__ Hs,
+                                                       long long img_stride, long long pre_stride,
+                                                       long long vol_stride) {
     __shared__ unsigned char ring[11][256];
     const int tid = threadIdx.x, spb = 256 / D, seg = tid / D, d = tid - seg * D;
     if (seg >= spb) return;
@@ -118,6 +146,11 @@ __global__ __launch_bounds__(256) void k_sgm_cost_rows(const uint8_t* __restrict
     const int xs = maxD + (blockIdx.x * spb + seg) * SGM_SEG;
     if (xs >= W) return;
     const int xe = min(xs + SGM_SEG, W);
+    if (const unsigned sid = stream_index(blockIdx.z)) {
+        stream_branch();
+        seek_stream(gl, sid, img_stride), seek_stream(gr, sid, img_stride);
+        seek_stream(pl, sid, pre_stride), seek_stream(pr, sid, pre_stride), seek_stream(Hs, sid, vol_stride);
+    }
     const size_t o = (size_t)y * W;
     gl += o, gr += o, pl += o, pr += o;
     int sum = 0, last_cx = -1, last_val = 0, slot = 0;
@@ -151,9 +184,13 @@ __device__ __forceinline__ void ld4(const uint16_t* p, int (&v)[4]) {
     v[0] = t.x & 0xffff, v[1] = t.x >> 16, v[2] = t.y & 0xffff, v[3] = t.y >> 16;
 }
 __global__ __launch_bounds__(256) void k_sgm_cost_cols(const uint16_t* __restrict__ Hs, int H, int W, int maxD, int D,
-                                                       int bs, uint16_t* __restrict__ C) {
+                                                       int bs, uint16_t* __restrict__ C, long long vol_stride) {
     const long long n = (long long)(W - maxD) * D, e = 4ll * (blockIdx.x * 256 + threadIdx.x);
     if (e >= n) return;
+    if (const unsigned sid = stream_index(blockIdx.z)) {
+        stream_branch();
+        seek_stream(Hs, sid, vol_stride), seek_stream(C, sid, vol_stride);
+    }
     const size_t pitch = (size_t)W * D, base = (size_t)maxD * D + e;
     const int r = bs / 2, ys = blockIdx.y * SGM_YSEG, ye = min(ys + SGM_YSEG, H);
     int sum[4] = {0, 0, 0, 0}, v[4], w[4];
@@ -241,12 +278,12 @@ constexpr int SGM_PF = 8;
 // top -> down: one wave per column x >= maxD, four adjacent columns per block; S = L
 template <int NK, bool FULL>
 __global__ __launch_bounds__(256) void k_sgm_down(const uint16_t* __restrict__ C, int H, int W, int maxD, int D, int P1,
-                                                  int P2, uint16_t* __restrict__ S) {
+                                                  int P2, uint16_t* __restrict__ S, long long vol_stride) {
     const int lane = threadIdx.x & 63, x = maxD + blockIdx.x * 4 + (threadIdx.x >> 6);
     if (x >= W) return;
-    const size_t pitch = (size_t)W * D;
-    const uint16_t* c = C + (size_t)x * D;
-    uint16_t* s = S + (size_t)x * D;
+    const size_t pitch = (size_t)W * D, so = stream_off(blockIdx.y, vol_stride);
+    const uint16_t* c = C + so + (size_t)x * D;
+    uint16_t* s = S + so + (size_t)x * D;
     int L[NK], ring[SGM_PF][NK];
     path_init<NK, FULL>(L, lane, D);
 #pragma unroll
@@ -274,9 +311,9 @@ __global__ __launch_bounds__(256) void k_sgm_down(const uint16_t* __restrict__ C
 // left -> right: one wave per row; S += L
 template <int NK, bool FULL>
 __global__ __launch_bounds__(64) void k_sgm_right(const uint16_t* __restrict__ C, int W, int maxD, int D, int P1, int P2,
-                                                  uint16_t* __restrict__ S) {
+                                                  uint16_t* __restrict__ S, long long vol_stride) {
     const int lane = threadIdx.x, n = W - maxD;
-    const size_t row = ((size_t)blockIdx.x * W + maxD) * D;
+    const size_t row = stream_off(blockIdx.y, vol_stride) + ((size_t)blockIdx.x * W + maxD) * D;
     const uint16_t* c = C + row;
     uint16_t* s = S + row;
     int L[NK], rc[SGM_PF][NK], rs[SGM_PF][NK];
@@ -343,14 +380,16 @@ __device__ __forceinline__ void walk_advance(SgmCursor& c, const SgmWalk& w, boo
 }
 template <int NK, bool FULL, bool ACC>
 __global__ __launch_bounds__(256) void k_sgm_walk(const uint16_t* __restrict__ C, int H, int W, int maxD, int D, int P1,
-                                                  int P2, int dy, int dx, int lines, int T, uint16_t* __restrict__ S) {
+                                                  int P2, int dy, int dx, int lines, int T, uint16_t* __restrict__ S,
+                                                  long long vol_stride) {
     const int lane = threadIdx.x & 63;
     const int line = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (line >= lines) return;
     const int n = W - maxD;
     const long long pitch = (long long)W * D;
-    const uint16_t* c = C + (size_t)maxD * D;
-    uint16_t* s = S + (size_t)maxD * D;
+    const size_t so = stream_off(blockIdx.y, vol_stride) + (size_t)maxD * D;
+    const uint16_t* c = C + so;
+    uint16_t* s = S + so;
     SgmWalk w;
     w.dx = dx;
     w.inc = dy * pitch + dx * D;
@@ -471,7 +510,8 @@ template <int NK, bool FULL, bool TOTAL>
 __global__ __launch_bounds__(64) void k_sgm_left(const uint16_t* __restrict__ C, const uint16_t* __restrict__ S, int W,
                                                  int minD, int D, int P1, int P2, int uniq, int max_diff,
                                                  uint16_t* __restrict__ S_total, int16_t* __restrict__ q_raw,
-                                                 int16_t* __restrict__ q_out) {
+                                                 int16_t* __restrict__ q_out, long long vol_stride,
+                                                 long long img_stride) {
     extern __shared__ int sgm_lds[];
     int* key2 = sgm_lds;  // [W + 1]
     SgmRow row_lds;
@@ -488,7 +528,7 @@ __global__ __launch_bounds__(64) void k_sgm_left(const uint16_t* __restrict__ C,
     if (n > 0) {
         // scan step t is pixel x = W - 1 - t. The winner of pixel t - 1 is taken inside the step of pixel t: two
         // independent instruction streams in one basic block. The first call works on zeros and stores to slot W.
-        const size_t row = ((size_t)y * W + (W - 1)) * D;  // step 0
+        const size_t row = stream_off(blockIdx.y, vol_stride) + ((size_t)y * W + (W - 1)) * D;  // step 0, this stream
         const uint16_t* c = C + row;
         const uint16_t* s = S + row;
         int L[NK], prev[NK], rc[SGM_PF][NK], rs[SGM_PF][NK];
@@ -531,6 +571,11 @@ __global__ __launch_bounds__(64) void k_sgm_left(const uint16_t* __restrict__ C,
         winner_px<NK>(prev, maxD, lane, D, uniq, row_lds);
     }
     __syncthreads();
+    {  // the disparity maps are not touched by the scan: their stream offset is folded in here, after it
+        const size_t qo = stream_off(blockIdx.y, img_stride);
+        q_out += qo;
+        if (q_raw) q_raw += qo;
+    }
     for (int x = lane; x < W; x += 64) {
         int q = invalid;
         if (x >= maxD && r_best[x] >= 0) {
@@ -610,8 +655,13 @@ __device__ __forceinline__ bool sp_joined(int a, int b, int invalid, int lim) {
 // One wave per 64 pixels of a row: every pixel starts linked to the first pixel of its horizontal run inside the
 // segment (the highest run start at or below the lane, from one ballot), so most horizontal unions never happen.
 __global__ __launch_bounds__(256) void k_speckle_init(const int16_t* __restrict__ q, int H, int W, int invalid, int lim,
-                                                      int* __restrict__ parent, int* __restrict__ count) {
+                                                      int* __restrict__ parent, int* __restrict__ count,
+                                                      long long img_stride, long long work_stride) {
     const int lane = threadIdx.x & 63, nseg = (W + 63) / 64, total = H * nseg;
+    if (const unsigned sid = stream_index(blockIdx.y)) {
+        stream_branch();
+        seek_stream(q, sid, img_stride), seek_stream(parent, sid, work_stride), seek_stream(count, sid, work_stride);
+    }
     for (int w = blockIdx.x * 4 + (threadIdx.x >> 6); w < total; w += gridDim.x * 4) {
         const int y = w / nseg, x = (w - y * nseg) * 64 + lane;
         const bool in = x < W;
@@ -631,8 +681,12 @@ __global__ __launch_bounds__(256) void k_speckle_init(const int16_t* __restrict_
 // The remaining edges: horizontal ones across a segment boundary, and vertical ones, except where the edge one
 // column to the left joins the same two runs (its own union, or by induction the one further left, covers it).
 __global__ __launch_bounds__(256) void k_speckle_link(const int16_t* __restrict__ q, int H, int W, int invalid, int lim,
-                                                      int* parent) {
+                                                      int* parent, long long img_stride, long long work_stride) {
     const int P = H * W;
+    if (const unsigned sid = stream_index(blockIdx.y)) {
+        stream_branch();
+        seek_stream(q, sid, img_stride), seek_stream(parent, sid, work_stride);
+    }
     for (int i = blockIdx.x * 256 + threadIdx.x; i < P; i += gridDim.x * 256) {
         const int v = q[i];
         if (v == invalid) continue;
@@ -652,8 +706,12 @@ __global__ __launch_bounds__(256) void k_speckle_link(const int16_t* __restrict_
 // after the links are final: the root of every valid pixel (stored back: a plain shortening of its own path) and the
 // component sizes at the roots, one atomicAdd per distinct root of a wave
 __global__ __launch_bounds__(256) void k_speckle_count(const int16_t* __restrict__ q, int P, int invalid, int* parent,
-                                                       int* count) {
+                                                       int* count, long long img_stride, long long work_stride) {
     const int lane = threadIdx.x & 63;
+    if (const unsigned sid = stream_index(blockIdx.y)) {
+        stream_branch();
+        seek_stream(q, sid, img_stride), seek_stream(parent, sid, work_stride), seek_stream(count, sid, work_stride);
+    }
     for (int i0 = blockIdx.x * 256 + (threadIdx.x & ~63); i0 < P; i0 += gridDim.x * 256) {
         const int i = i0 + lane;
         bool todo = i < P && q[i] != invalid;
@@ -674,7 +732,12 @@ __global__ __launch_bounds__(256) void k_speckle_count(const int16_t* __restrict
     }
 }
 __global__ __launch_bounds__(256) void k_speckle_apply(int16_t* __restrict__ q, int P, int invalid, int window,
-                                                       const int* __restrict__ parent, const int* __restrict__ count) {
+                                                       const int* __restrict__ parent, const int* __restrict__ count,
+                                                       long long img_stride, long long work_stride) {
+    if (const unsigned sid = stream_index(blockIdx.y)) {
+        stream_branch();
+        seek_stream(q, sid, img_stride), seek_stream(parent, sid, work_stride), seek_stream(count, sid, work_stride);
+    }
     for (int i = blockIdx.x * 256 + threadIdx.x; i < P; i += gridDim.x * 256) {
         if (q[i] == invalid) continue;
         if (count[uf_find(parent, i)] <= window) q[i] = (int16_t)invalid;
@@ -685,17 +748,29 @@ __global__ __launch_bounds__(256) void k_speckle_apply(int16_t* __restrict__ q, 
 struct SgmQ {
     double q2[4], q3[4];  // rows 2 and 3 of the 4 x 4 reprojection matrix
 };
-__global__ void k_sgm_mm_init(unsigned* mm) {
+__global__ void k_sgm_mm_init(unsigned* mm) {  // one block per stream
     if (threadIdx.x == 0) {
-        mm[0] = 0xffffffffu;
-        mm[1] = 0u;
+        mm[2 * blockIdx.x] = 0xffffffffu;
+        mm[2 * blockIdx.x + 1] = 0u;
     }
 }
 // disp = q / 16 (NaN where <= 0), z in fp64 from nan_to_num(disp), and the min / max of nan_to_num(disp): its values
-// are >= 0, so they order like their bit patterns
+// are >= 0, so they order like their bit patterns. QDEV: the rows come from Qdev, f64 [n][16] on the device, one matrix
+// per stream; else from Q, by value (the single-stream entry point: they stay in scalar registers). mm: [n][2]
+template <bool QDEV>
 __global__ __launch_bounds__(256) void k_sgm_post(const int16_t* __restrict__ q, int H, int W, SgmQ Q,
-                                                  float* __restrict__ disp, float* __restrict__ z, unsigned* mm) {
+                                                  const double* __restrict__ Qdev, float* __restrict__ disp,
+                                                  float* __restrict__ z, unsigned* mm) {
     const int P = H * W;
+    if (const unsigned sid = stream_index(blockIdx.y)) {
+        stream_branch();
+        seek_stream(q, sid, P), seek_stream(disp, sid, P), seek_stream(z, sid, P), seek_stream(mm, sid, 2);
+        if (QDEV) seek_stream(Qdev, sid, 16);
+    }
+    if (QDEV) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Q.q2[i] = Qdev[8 + i], Q.q3[i] = Qdev[12 + i];
+    }
     unsigned lo = 0xffffffffu, hi = 0u;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < P; i += gridDim.x * 256) {
         const int y = i / W, x = i - y * W;
@@ -732,6 +807,10 @@ __global__ __launch_bounds__(256) void k_sgm_post(const int16_t* __restrict__ q,
 // cv2.normalize(NORM_MINMAX, 0, 255) + astype(uint8) as stated: trunc(float32(v * scale + shift)), fp64 scale / shift
 __global__ __launch_bounds__(256) void k_sgm_code(const float* __restrict__ disp, int P, const unsigned* __restrict__ mm,
                                                   uint8_t* __restrict__ code) {
+    if (const unsigned sid = stream_index(blockIdx.y)) {
+        stream_branch();
+        seek_stream(disp, sid, P), seek_stream(code, sid, P), seek_stream(mm, sid, 2);
+    }
     const double lo = (double)__uint_as_float(mm[0]), hi = (double)__uint_as_float(mm[1]);
     const double scale = hi != lo ? 255.0 / (hi - lo) : 0.0;
     const double shift = -lo * scale;
@@ -746,7 +825,11 @@ __global__ __launch_bounds__(256) void k_sgm_code(const float* __restrict__ disp
 // value counts, infinities and negatives included (sd_live_center keeps only finite, > 0 values). Bitonic sort in LDS,
 // padded with +inf; even count: the float32 mean of the two middle values; no value: NaN.
 __global__ __launch_bounds__(256) void k_sgm_center(const float* __restrict__ src, int H, int W, int window,
-                                                    float* __restrict__ out) {
+                                                    float* __restrict__ out) {  // one block per stream
+    if (const unsigned sid = stream_index(blockIdx.x)) {
+        stream_branch();
+        seek_stream(src, sid, (long long)H * W), out += sid;
+    }
     __shared__ float buf[4096];
     __shared__ int s_cnt;
     if (threadIdx.x == 0) s_cnt = 0;
@@ -790,62 +873,80 @@ __global__ __launch_bounds__(256) void k_sgm_center(const float* __restrict__ sr
 }
 
 // ------------------------------------------------------------------ launches
-int launch_cost(const uint8_t* gl, const uint8_t* gr, const uint8_t* pl, const uint8_t* pr, int H, int W,
-                const SgmParams& p, uint16_t* C, uint16_t* tmp, hipStream_t st) {
+// The streams of a launch and the distances between their slices: img in elements of an image plane (gray, q), pre in
+// bytes between the prefiltered planes, vol in uint16 elements between the volumes, spk in int32 elements between the
+// speckle planes. A single-stream entry point passes SGM_ONE; a slice of the batched workspace is the single-stream
+// workspace, so pre, vol and spk are all its size there.
+struct SgmBatch {
+    int n;
+    long long img, pre, vol, spk;
+};
+constexpr SgmBatch SGM_ONE = {1, 0, 0, 0, 0};
+
+int launch_cost(const SgmBatch& nb, const uint8_t* gl, const uint8_t* gr, const uint8_t* pl, const uint8_t* pr, int H,
+                int W, const SgmParams& p, uint16_t* C, uint16_t* tmp, hipStream_t st) {
     const int maxD = p.minD + p.D;
     if (W <= maxD) return SD_OK;
     const int nseg = cdiv(W - maxD, SGM_SEG), spb = 256 / p.D;
-    hipLaunchKernelGGL(k_sgm_cost_rows, dim3(cdiv(nseg, spb), H), dim3(256), 0, st, gl, gr, pl, pr, W, p.minD, p.D, p.bs,
-                       tmp);
-    hipLaunchKernelGGL(k_sgm_cost_cols, dim3(cdiv((long long)(W - maxD) * p.D, 1024), cdiv(H, SGM_YSEG)), dim3(256), 0,
-                       st, tmp, H, W, maxD, p.D, p.bs, C);
+    // grid y is the row (cost_rows) or the row segment (cost_cols): the stream goes in z
+    hipLaunchKernelGGL(k_sgm_cost_rows, dim3(cdiv(nseg, spb), H, nb.n), dim3(256), 0, st, gl, gr, pl, pr, W, p.minD, p.D,
+                       p.bs, tmp, nb.img, nb.pre, nb.vol);
+    hipLaunchKernelGGL(k_sgm_cost_cols, dim3(cdiv((long long)(W - maxD) * p.D, 1024), cdiv(H, SGM_YSEG), nb.n), dim3(256),
+                       0, st, tmp, H, W, maxD, p.D, p.bs, C, nb.vol);
     return sd_check_launch("sd_sgm_cost");
 }
 
 template <int NK, bool FULL>
-void launch_path(int pass, const uint16_t* C, int H, int W, const SgmParams& p, uint16_t* S, hipStream_t st) {
+void launch_path(const SgmBatch& nb, int pass, const uint16_t* C, int H, int W, const SgmParams& p, uint16_t* S,
+                 hipStream_t st) {
     const int maxD = p.minD + p.D;
     if (pass == 0)
-        hipLaunchKernelGGL((k_sgm_down<NK, FULL>), dim3(cdiv(W - maxD, 4)), dim3(256), 0, st, C, H, W, maxD, p.D, p.P1,
-                           p.P2, S);
+        hipLaunchKernelGGL((k_sgm_down<NK, FULL>), dim3(cdiv(W - maxD, 4), nb.n), dim3(256), 0, st, C, H, W, maxD, p.D,
+                           p.P1, p.P2, S, nb.vol);
     else
-        hipLaunchKernelGGL((k_sgm_right<NK, FULL>), dim3(H), dim3(64), 0, st, C, W, maxD, p.D, p.P1, p.P2, S);
+        hipLaunchKernelGGL((k_sgm_right<NK, FULL>), dim3(H, nb.n), dim3(64), 0, st, C, W, maxD, p.D, p.P1, p.P2, S,
+                           nb.vol);
 }
-int launch_aggregate(int pass, const uint16_t* C, int H, int W, const SgmParams& p, uint16_t* S, hipStream_t st) {
+int launch_aggregate(const SgmBatch& nb, int pass, const uint16_t* C, int H, int W, const SgmParams& p, uint16_t* S,
+                     hipStream_t st) {
     if (W <= p.minD + p.D) return SD_OK;
     const bool full = p.D % 64 == 0;
+#define SGM_PATH(NK)                                                \
+    (full ? launch_path<NK, true>(nb, pass, C, H, W, p, S, st)     \
+          : launch_path<NK, false>(nb, pass, C, H, W, p, S, st))
     switch ((p.D + 63) / 64) {
-    case 1: full ? launch_path<1, true>(pass, C, H, W, p, S, st) : launch_path<1, false>(pass, C, H, W, p, S, st); break;
-    case 2: full ? launch_path<2, true>(pass, C, H, W, p, S, st) : launch_path<2, false>(pass, C, H, W, p, S, st); break;
-    case 3: full ? launch_path<3, true>(pass, C, H, W, p, S, st) : launch_path<3, false>(pass, C, H, W, p, S, st); break;
-    default: full ? launch_path<4, true>(pass, C, H, W, p, S, st) : launch_path<4, false>(pass, C, H, W, p, S, st); break;
+    case 1: SGM_PATH(1); break;
+    case 2: SGM_PATH(2); break;
+    case 3: SGM_PATH(3); break;
+    default: SGM_PATH(4); break;
     }
+#undef SGM_PATH
     return sd_check_launch("sd_sgm_aggregate");
 }
 
 template <int NK, bool FULL>
-void launch_walk(const uint16_t* C, int H, int W, const SgmParams& p, int dy, int dx, bool acc, uint16_t* S,
-                 hipStream_t st) {
+void launch_walk(const SgmBatch& nb, const uint16_t* C, int H, int W, const SgmParams& p, int dy, int dx, bool acc,
+                 uint16_t* S, hipStream_t st) {
     const int maxD = p.minD + p.D, n = W - maxD;
     const int lines = dy == 0 ? H : n, T = dy == 0 ? n : H;
     if (acc)
-        hipLaunchKernelGGL((k_sgm_walk<NK, FULL, true>), dim3(cdiv(lines, 4)), dim3(256), 0, st, C, H, W, maxD, p.D, p.P1,
-                           p.P2, dy, dx, lines, T, S);
+        hipLaunchKernelGGL((k_sgm_walk<NK, FULL, true>), dim3(cdiv(lines, 4), nb.n), dim3(256), 0, st, C, H, W, maxD, p.D,
+                           p.P1, p.P2, dy, dx, lines, T, S, nb.vol);
     else
-        hipLaunchKernelGGL((k_sgm_walk<NK, FULL, false>), dim3(cdiv(lines, 4)), dim3(256), 0, st, C, H, W, maxD, p.D, p.P1,
-                           p.P2, dy, dx, lines, T, S);
+        hipLaunchKernelGGL((k_sgm_walk<NK, FULL, false>), dim3(cdiv(lines, 4), nb.n), dim3(256), 0, st, C, H, W, maxD, p.D,
+                           p.P1, p.P2, dy, dx, lines, T, S, nb.vol);
 }
 // one path (dy, dx) other than right -> left: S = L (acc false) or S += L. Top -> down writing S and left -> right
 // adding to it are the 3-way mode's own kernels.
-int launch_dir(const uint16_t* C, int H, int W, const SgmParams& p, int dy, int dx, bool acc, uint16_t* S,
-               hipStream_t st) {
+int launch_dir(const SgmBatch& nb, const uint16_t* C, int H, int W, const SgmParams& p, int dy, int dx, bool acc,
+               uint16_t* S, hipStream_t st) {
     if (W <= p.minD + p.D) return SD_OK;
-    if (dy == 1 && dx == 0 && !acc) return launch_aggregate(0, C, H, W, p, S, st);
-    if (dy == 0 && dx == 1 && acc) return launch_aggregate(1, C, H, W, p, S, st);
+    if (dy == 1 && dx == 0 && !acc) return launch_aggregate(nb, 0, C, H, W, p, S, st);
+    if (dy == 0 && dx == 1 && acc) return launch_aggregate(nb, 1, C, H, W, p, S, st);
     const bool full = p.D % 64 == 0;
-#define SGM_WALK(NK)                                                      \
-    (full ? launch_walk<NK, true>(C, H, W, p, dy, dx, acc, S, st)        \
-          : launch_walk<NK, false>(C, H, W, p, dy, dx, acc, S, st))
+#define SGM_WALK(NK)                                                          \
+    (full ? launch_walk<NK, true>(nb, C, H, W, p, dy, dx, acc, S, st)        \
+          : launch_walk<NK, false>(nb, C, H, W, p, dy, dx, acc, S, st))
     switch ((p.D + 63) / 64) {
     case 1: SGM_WALK(1); break;
     case 2: SGM_WALK(2); break;
@@ -857,22 +958,22 @@ int launch_dir(const uint16_t* C, int H, int W, const SgmParams& p, int dy, int 
 }
 
 template <int NK, bool FULL>
-void launch_left(const uint16_t* C, const uint16_t* S, int H, int W, const SgmParams& p, uint16_t* S_total,
-                 int16_t* q_raw, int16_t* q, hipStream_t st) {
+void launch_left(const SgmBatch& nb, const uint16_t* C, const uint16_t* S, int H, int W, const SgmParams& p,
+                 uint16_t* S_total, int16_t* q_raw, int16_t* q, hipStream_t st) {
     const size_t lds = (size_t)(W + 1) * 14;
     if (S_total)
-        hipLaunchKernelGGL((k_sgm_left<NK, FULL, true>), dim3(H), dim3(64), lds, st, C, S, W, p.minD, p.D, p.P1, p.P2,
-                           p.uniq, p.max_diff, S_total, q_raw, q);
+        hipLaunchKernelGGL((k_sgm_left<NK, FULL, true>), dim3(H, nb.n), dim3(64), lds, st, C, S, W, p.minD, p.D, p.P1,
+                           p.P2, p.uniq, p.max_diff, S_total, q_raw, q, nb.vol, nb.img);
     else
-        hipLaunchKernelGGL((k_sgm_left<NK, FULL, false>), dim3(H), dim3(64), lds, st, C, S, W, p.minD, p.D, p.P1, p.P2,
-                           p.uniq, p.max_diff, S_total, q_raw, q);
+        hipLaunchKernelGGL((k_sgm_left<NK, FULL, false>), dim3(H, nb.n), dim3(64), lds, st, C, S, W, p.minD, p.D, p.P1,
+                           p.P2, p.uniq, p.max_diff, S_total, q_raw, q, nb.vol, nb.img);
 }
-int launch_winner(const uint16_t* C, const uint16_t* S, int H, int W, const SgmParams& p, uint16_t* S_total,
-                  int16_t* q_raw, int16_t* q, hipStream_t st) {
+int launch_winner(const SgmBatch& nb, const uint16_t* C, const uint16_t* S, int H, int W, const SgmParams& p,
+                  uint16_t* S_total, int16_t* q_raw, int16_t* q, hipStream_t st) {
     const bool full = p.D % 64 == 0;
-#define SGM_LEFT(NK)                                                         \
-    (full ? launch_left<NK, true>(C, S, H, W, p, S_total, q_raw, q, st)     \
-          : launch_left<NK, false>(C, S, H, W, p, S_total, q_raw, q, st))
+#define SGM_LEFT(NK)                                                             \
+    (full ? launch_left<NK, true>(nb, C, S, H, W, p, S_total, q_raw, q, st)     \
+          : launch_left<NK, false>(nb, C, S, H, W, p, S_total, q_raw, q, st))
     switch ((p.D + 63) / 64) {
     case 1: SGM_LEFT(1); break;
     case 2: SGM_LEFT(2); break;
@@ -883,19 +984,24 @@ int launch_winner(const uint16_t* C, const uint16_t* S, int H, int W, const SgmP
     return sd_check_launch("sd_sgm_winner");
 }
 
-int launch_speckle(int16_t* q, int H, int W, int invalid, int window, int range, void* work, hipStream_t st) {
+// Every stream's pixels index its own parent / count planes from 0 (nb.img, nb.spk apart): a link can only name a
+// pixel of the same stream, so no component crosses a stream boundary.
+int launch_speckle(const SgmBatch& nb, int16_t* q, int H, int W, int invalid, int window, int range, void* work,
+                   hipStream_t st) {
     if (window <= 0) return SD_OK;
     const int P = H * W;
     int* parent = static_cast<int*>(work);
     int* count = reinterpret_cast<int*>(static_cast<char*>(work) + align256(4ll * P));
-    const dim3 g(sgm_grid(P)), b(256);
-    hipLaunchKernelGGL(k_speckle_init, dim3(sgm_grid(64ll * H * ((W + 63) / 64))), b, 0, st, q, H, W, invalid, 16 * range, parent,
-                       count);
-    hipLaunchKernelGGL(k_speckle_link, g, b, 0, st, q, H, W, invalid, 16 * range, parent);
-    hipLaunchKernelGGL(k_speckle_count, g, b, 0, st, q, P, invalid, parent, count);
-    hipLaunchKernelGGL(k_speckle_apply, g, b, 0, st, q, P, invalid, window, parent, count);
+    const dim3 g(sgm_grid(P), nb.n), b(256);
+    hipLaunchKernelGGL(k_speckle_init, dim3(sgm_grid(64ll * H * ((W + 63) / 64)), nb.n), b, 0, st, q, H, W, invalid,
+                       16 * range, parent, count, nb.img, nb.spk);
+    hipLaunchKernelGGL(k_speckle_link, g, b, 0, st, q, H, W, invalid, 16 * range, parent, nb.img, nb.spk);
+    hipLaunchKernelGGL(k_speckle_count, g, b, 0, st, q, P, invalid, parent, count, nb.img, nb.spk);
+    hipLaunchKernelGGL(k_speckle_apply, g, b, 0, st, q, P, invalid, window, parent, count, nb.img, nb.spk);
     return sd_check_launch("sd_sgm_speckle");
 }
+bool sgm_streams_ok(int n) { return n >= 1 && n <= 64; }
+#define SGM_N_REQUIRE(fn, n) SD_REQUIRE(sgm_streams_ok(n), "%s: n = %d streams (1..64)", fn, n)
 
 #define SGM_PARAMS_OK(what, p)                                     \
     do {                                                           \
@@ -923,7 +1029,8 @@ extern "C" int sd_sgm_prefilter(const uint8_t* gray, int H, int W, int cap, uint
     SD_REQUIRE(gray && out, "sd_sgm_prefilter: null pointer");
     SD_REQUIRE(sgm_dims_ok(H, W), "sd_sgm_prefilter: bad sizes %dx%d", H, W);
     SD_REQUIRE(cap >= 1 && cap <= 63, "sd_sgm_prefilter: cap %d (1..63)", cap);
-    hipLaunchKernelGGL(k_sgm_prefilter, dim3(sgm_grid((long long)H * W)), dim3(256), 0, to_stream(s), gray, H, W, cap, out);
+    hipLaunchKernelGGL(k_sgm_prefilter, dim3(sgm_grid((long long)H * W)), dim3(256), 0, to_stream(s), gray, H, W, cap, out,
+                       0ll, 0ll);
     return sd_check_launch("sd_sgm_prefilter");
 }
 
@@ -935,7 +1042,7 @@ extern "C" int sd_sgm_cost(const uint8_t* gray_l, const uint8_t* gray_r, const u
     SD_REQUIRE(sgm_dims_ok(H, W) && H <= 65535, "sd_sgm_cost: bad sizes %dx%d", H, W);
     const SgmParams p = {min_disparity, num_disparities, block_size, 0, 0, 1, 0, 0, 0, 31};
     SGM_PARAMS_OK("sd_sgm_cost", p);
-    return launch_cost(gray_l, gray_r, pre_l, pre_r, H, W, p, C, tmp, to_stream(s));
+    return launch_cost(SGM_ONE, gray_l, gray_r, pre_l, pre_r, H, W, p, C, tmp, to_stream(s));
 }
 
 extern "C" int sd_sgm_aggregate(const uint16_t* C, int H, int W, int min_disparity, int num_disparities, int P1, int P2,
@@ -945,7 +1052,7 @@ extern "C" int sd_sgm_aggregate(const uint16_t* C, int H, int W, int min_dispari
     SD_REQUIRE(pass == 0 || pass == 1, "sd_sgm_aggregate: pass %d (0 top-down, 1 left-right)", pass);
     const SgmParams p = {min_disparity, num_disparities, 3, P1, P2, 1, 0, 0, 0, 1};
     SGM_PARAMS_OK("sd_sgm_aggregate", p);
-    return launch_aggregate(pass, C, H, W, p, S, to_stream(s));
+    return launch_aggregate(SGM_ONE, pass, C, H, W, p, S, to_stream(s));
 }
 
 extern "C" int sd_sgm_aggregate_dir(const uint16_t* C, int H, int W, int min_disparity, int num_disparities, int P1,
@@ -959,7 +1066,7 @@ extern "C" int sd_sgm_aggregate_dir(const uint16_t* C, int H, int W, int min_dis
     SD_REQUIRE(accumulate == 0 || accumulate == 1, "sd_sgm_aggregate_dir: accumulate %d (0: S = L, 1: S += L)", accumulate);
     const SgmParams p = {min_disparity, num_disparities, 3, P1, P2, 1, 0, 0, 0, 1};
     SGM_PARAMS_OK("sd_sgm_aggregate_dir", p);
-    return launch_dir(C, H, W, p, dy, dx, accumulate != 0, S, to_stream(s));
+    return launch_dir(SGM_ONE, C, H, W, p, dy, dx, accumulate != 0, S, to_stream(s));
 }
 
 extern "C" int sd_sgm_winner(const uint16_t* C, const uint16_t* S, int H, int W, int min_disparity, int num_disparities,
@@ -969,29 +1076,47 @@ extern "C" int sd_sgm_winner(const uint16_t* C, const uint16_t* S, int H, int W,
     SD_REQUIRE(sgm_dims_ok(H, W) && W <= SGM_MAX_W, "sd_sgm_winner: bad sizes %dx%d (W <= %d)", H, W, SGM_MAX_W);
     const SgmParams p = {min_disparity, num_disparities, 3, P1, P2, disp12_max_diff, uniqueness_ratio, 0, 0, 1};
     SGM_PARAMS_OK("sd_sgm_winner", p);
-    return launch_winner(C, S, H, W, p, S_total, q_raw, q, to_stream(s));
+    return launch_winner(SGM_ONE, C, S, H, W, p, S_total, q_raw, q, to_stream(s));
 }
+
+namespace {
+// sd_sgm_speckle (n = 1) and sd_sgm_speckle_n: q is [n][H][W], work n slices of sd_sgm_speckle_ws_bytes
+int sgm_speckle(const char* fn, int n, int16_t* q, int H, int W, int invalid_value, int window, int range, void* work,
+                sd_stream s) {
+    SGM_N_REQUIRE(fn, n);
+    SD_REQUIRE(q && (work || window <= 0), "%s: null pointer (q, work)", fn);
+    SD_REQUIRE(sgm_dims_ok(H, W), "%s: bad sizes %dx%d", fn, H, W);
+    SD_REQUIRE(window >= 0 && range >= 0 && range <= 1024, "%s: window %d range %d", fn, window, range);
+    SD_REQUIRE((uintptr_t)work % 4 == 0, "%s: work must be 4-B aligned", fn);
+    const SgmBatch nb = {n, (long long)H * W, 0, 0, sd_sgm_speckle_ws_bytes(H, W) / 4};
+    return launch_speckle(nb, q, H, W, invalid_value, window, range, work, to_stream(s));
+}
+}  // namespace
 
 extern "C" int sd_sgm_speckle(int16_t* q, int H, int W, int invalid_value, int window, int range, void* work,
                               sd_stream s) {
-    SD_REQUIRE(q && (work || window <= 0), "sd_sgm_speckle: null pointer");
-    SD_REQUIRE(sgm_dims_ok(H, W), "sd_sgm_speckle: bad sizes %dx%d", H, W);
-    SD_REQUIRE(window >= 0 && range >= 0 && range <= 1024, "sd_sgm_speckle: window %d range %d", window, range);
-    SD_REQUIRE((uintptr_t)work % 4 == 0, "sd_sgm_speckle: work must be 4-B aligned");
-    return launch_speckle(q, H, W, invalid_value, window, range, work, to_stream(s));
+    return sgm_speckle("sd_sgm_speckle", 1, q, H, W, invalid_value, window, range, work, s);
+}
+extern "C" int sd_sgm_speckle_n(int n, int16_t* q, int H, int W, int invalid_value, int window, int range, void* work,
+                                sd_stream s) {
+    return sgm_speckle("sd_sgm_speckle_n", n, q, H, W, invalid_value, window, range, work, s);
 }
 
 namespace {
 // the vertical-family paths a mode adds to the 3-way mode's three, as (dy, dx)
 const int SGM_EXTRA_PATHS[5][2] = {{1, 1}, {1, -1}, {-1, 0}, {-1, 1}, {-1, -1}};
-int sgm_compute(const char* what, const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, const SgmParams& p,
+// The whole matcher for n streams: gray_l, gray_r [n][H][W], q [n][H][W], work n slices of sd_sgm_ws_bytes. One launch
+// sequence whatever n is; the single-stream entry points are n = 1.
+int sgm_compute(const char* what, int n, const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, const SgmParams& p,
                 int mode, void* work, int16_t* q, sd_stream s) {
-    SD_REQUIRE(gray_l && gray_r && work && q, "%s: null pointer", what);
+    SGM_N_REQUIRE(what, n);
+    SD_REQUIRE(gray_l && gray_r && work && q, "%s: null pointer (gray_l, gray_r, work, q)", what);
     SD_REQUIRE(sgm_dims_ok(H, W) && H <= 65535 && W <= SGM_MAX_W, "%s: bad sizes %dx%d (W <= %d)", what, H, W, SGM_MAX_W);
     SD_REQUIRE((uintptr_t)work % 256 == 0, "%s: work must be 256-B aligned", what);
     const char* e = sgm_params_error(p);
     SD_REQUIRE(!e, "%s: %s", what, e);
-    const long long P = (long long)H * W, vol = align256(2 * P * p.D);
+    const long long P = (long long)H * W, vol = align256(2 * P * p.D), slice = sd_sgm_ws_bytes(H, W, p.D);
+    const SgmBatch nb = {n, P, slice, slice / 2, slice / 4};
     char* w = static_cast<char*>(work);
     uint16_t* C = reinterpret_cast<uint16_t*>(w);
     uint16_t* S = reinterpret_cast<uint16_t*>(w + vol);
@@ -999,22 +1124,38 @@ int sgm_compute(const char* what, const uint8_t* gray_l, const uint8_t* gray_r, 
     uint8_t* pr = pl + align256(P);
     void* sw = pr + align256(P);
     hipStream_t st = to_stream(s);
-    const dim3 g(sgm_grid(P)), b(256);
-    hipLaunchKernelGGL(k_sgm_prefilter, g, b, 0, st, gray_l, H, W, p.cap, pl);
-    hipLaunchKernelGGL(k_sgm_prefilter, g, b, 0, st, gray_r, H, W, p.cap, pr);
-    int rc = launch_cost(gray_l, gray_r, pl, pr, H, W, p, C, S, st);  // S is free until the first path writes it
-    if (rc == SD_OK) rc = launch_aggregate(0, C, H, W, p, S, st);
+    const dim3 g(sgm_grid(P), n), b(256);
+    hipLaunchKernelGGL(k_sgm_prefilter, g, b, 0, st, gray_l, H, W, p.cap, pl, nb.img, nb.pre);
+    hipLaunchKernelGGL(k_sgm_prefilter, g, b, 0, st, gray_r, H, W, p.cap, pr, nb.img, nb.pre);
+    int rc = launch_cost(nb, gray_l, gray_r, pl, pr, H, W, p, C, S, st);  // S is free until the first path writes it
+    if (rc == SD_OK) rc = launch_aggregate(nb, 0, C, H, W, p, S, st);
     // successive launches, each S += L: sgbm takes the two downward diagonals, hh4 bottom -> up, hh all five
     const int first = mode == SD_SGM_MODE_HH4 ? 2 : 0;
     const int last = mode == SD_SGM_MODE_HH4 ? 3 : mode == SD_SGM_MODE_SGBM ? 2 : mode == SD_SGM_MODE_HH ? 5 : 0;
     for (int i = first; i < last && rc == SD_OK; ++i)
-        rc = launch_dir(C, H, W, p, SGM_EXTRA_PATHS[i][0], SGM_EXTRA_PATHS[i][1], true, S, st);
-    if (rc == SD_OK) rc = launch_aggregate(1, C, H, W, p, S, st);
-    if (rc == SD_OK) rc = launch_winner(C, S, H, W, p, nullptr, nullptr, q, st);
-    if (rc == SD_OK) rc = launch_speckle(q, H, W, 16 * (p.minD - 1), p.speckle_window, p.speckle_range, sw, st);
+        rc = launch_dir(nb, C, H, W, p, SGM_EXTRA_PATHS[i][0], SGM_EXTRA_PATHS[i][1], true, S, st);
+    if (rc == SD_OK) rc = launch_aggregate(nb, 1, C, H, W, p, S, st);
+    if (rc == SD_OK) rc = launch_winner(nb, C, S, H, W, p, nullptr, nullptr, q, st);
+    if (rc == SD_OK) rc = launch_speckle(nb, q, H, W, 16 * (p.minD - 1), p.speckle_window, p.speckle_range, sw, st);
     return rc;
 }
 }  // namespace
+
+extern "C" long long sd_sgm_ws_bytes_n(int n, int H, int W, int D) {
+    return sgm_streams_ok(n) ? n * sd_sgm_ws_bytes(H, W, D) : -1;
+}
+
+extern "C" int sd_sgm_compute_n(int n, const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
+                                int num_disparities, int block_size, int P1, int P2, int disp12_max_diff,
+                                int uniqueness_ratio, int speckle_window, int speckle_range, int pre_filter_cap, int mode,
+                                void* work, int16_t* q, sd_stream s) {
+    SGM_N_REQUIRE("sd_sgm_compute_n", n);
+    const int npaths = sgm_mode_paths(mode);
+    SD_REQUIRE(npaths, "sd_sgm_compute_n: mode %d (SD_SGM_MODE_SGBM 0, _HH 1, _3WAY 2, _HH4 3)", mode);
+    const SgmParams p = {min_disparity, num_disparities, block_size, P1, P2, disp12_max_diff, uniqueness_ratio,
+                         speckle_window, speckle_range, pre_filter_cap, npaths};
+    return sgm_compute("sd_sgm_compute_n", n, gray_l, gray_r, H, W, p, mode, work, q, s);
+}
 
 extern "C" int sd_sgm_compute(const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
                               int num_disparities, int block_size, int P1, int P2, int disp12_max_diff,
@@ -1022,7 +1163,7 @@ extern "C" int sd_sgm_compute(const uint8_t* gray_l, const uint8_t* gray_r, int 
                               int16_t* q, sd_stream s) {
     const SgmParams p = {min_disparity, num_disparities, block_size, P1, P2, disp12_max_diff, uniqueness_ratio,
                          speckle_window, speckle_range, pre_filter_cap};
-    return sgm_compute("sd_sgm_compute", gray_l, gray_r, H, W, p, SD_SGM_MODE_3WAY, work, q, s);
+    return sgm_compute("sd_sgm_compute", 1, gray_l, gray_r, H, W, p, SD_SGM_MODE_3WAY, work, q, s);
 }
 
 extern "C" int sd_sgm_compute_mode(const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
@@ -1033,30 +1174,50 @@ extern "C" int sd_sgm_compute_mode(const uint8_t* gray_l, const uint8_t* gray_r,
     SD_REQUIRE(npaths, "sd_sgm_compute_mode: mode %d (SD_SGM_MODE_SGBM 0, _HH 1, _3WAY 2, _HH4 3)", mode);
     const SgmParams p = {min_disparity, num_disparities, block_size, P1, P2, disp12_max_diff, uniqueness_ratio,
                          speckle_window, speckle_range, pre_filter_cap, npaths};
-    return sgm_compute("sd_sgm_compute_mode", gray_l, gray_r, H, W, p, mode, work, q, s);
+    return sgm_compute("sd_sgm_compute_mode", 1, gray_l, gray_r, H, W, p, mode, work, q, s);
 }
+
+namespace {
+// sd_sgm_post (Q on the host, by value) and sd_sgm_post_n (Qdev: f64 [n][16] on the device); minmax is [n][2]
+int sgm_post(const char* fn, int n, const int16_t* q, int H, int W, const double* Qhost, const double* Qdev, float* disp,
+             float* z, uint8_t* code, unsigned* minmax, sd_stream s) {
+    SGM_N_REQUIRE(fn, n);
+    SD_REQUIRE(q && (Qhost || Qdev) && disp && z && code && minmax, "%s: null pointer (q, Q, disp, z, code, minmax)", fn);
+    SD_REQUIRE(sgm_dims_ok(H, W), "%s: bad sizes %dx%d", fn, H, W);
+    SgmQ m = {};
+    for (int i = 0; Qhost && i < 4; ++i) {
+        m.q2[i] = Qhost[8 + i];
+        m.q3[i] = Qhost[12 + i];
+    }
+    hipStream_t st = to_stream(s);
+    const dim3 g(sgm_grid((long long)H * W), n), b(256);
+    hipLaunchKernelGGL(k_sgm_mm_init, dim3(n), dim3(64), 0, st, minmax);
+    hipLaunchKernelGGL(Qdev ? k_sgm_post<true> : k_sgm_post<false>, g, b, 0, st, q, H, W, m, Qdev, disp, z, minmax);
+    hipLaunchKernelGGL(k_sgm_code, g, b, 0, st, disp, H * W, minmax, code);
+    return sd_check_launch(fn);
+}
+int sgm_center(const char* fn, int n, const float* z, int H, int W, int window, float* out, sd_stream s) {
+    SGM_N_REQUIRE(fn, n);
+    SD_REQUIRE(z && out, "%s: null pointer (z, out)", fn);
+    SD_REQUIRE(sgm_dims_ok(H, W), "%s: bad sizes %dx%d", fn, H, W);
+    SD_REQUIRE(window >= 0 && window <= 63, "%s: window %d (max 63)", fn, window);
+    hipLaunchKernelGGL(k_sgm_center, dim3(n), dim3(256), 0, to_stream(s), z, H, W, window, out);
+    return sd_check_launch(fn);
+}
+}  // namespace
 
 extern "C" int sd_sgm_post(const int16_t* q, int H, int W, const double* Q, float* disp, float* z, uint8_t* code,
                            unsigned* minmax, sd_stream s) {
-    SD_REQUIRE(q && Q && disp && z && code && minmax, "sd_sgm_post: null pointer");
-    SD_REQUIRE(sgm_dims_ok(H, W), "sd_sgm_post: bad sizes %dx%d", H, W);
-    SgmQ m;
-    for (int i = 0; i < 4; ++i) {
-        m.q2[i] = Q[8 + i];
-        m.q3[i] = Q[12 + i];
-    }
-    hipStream_t st = to_stream(s);
-    const dim3 g(sgm_grid((long long)H * W)), b(256);
-    hipLaunchKernelGGL(k_sgm_mm_init, dim3(1), dim3(64), 0, st, minmax);
-    hipLaunchKernelGGL(k_sgm_post, g, b, 0, st, q, H, W, m, disp, z, minmax);
-    hipLaunchKernelGGL(k_sgm_code, g, b, 0, st, disp, H * W, minmax, code);
-    return sd_check_launch("sd_sgm_post");
+    return sgm_post("sd_sgm_post", 1, q, H, W, Q, nullptr, disp, z, code, minmax, s);
+}
+extern "C" int sd_sgm_post_n(int n, const int16_t* q, int H, int W, const double* Qdev, float* disp, float* z,
+                             uint8_t* code, unsigned* minmax, sd_stream s) {
+    return sgm_post("sd_sgm_post_n", n, q, H, W, nullptr, Qdev, disp, z, code, minmax, s);
 }
 
 extern "C" int sd_sgm_center(const float* z, int H, int W, int window, float* out, sd_stream s) {
-    SD_REQUIRE(z && out, "sd_sgm_center: null pointer");
-    SD_REQUIRE(sgm_dims_ok(H, W), "sd_sgm_center: bad sizes %dx%d", H, W);
-    SD_REQUIRE(window >= 0 && window <= 63, "sd_sgm_center: window %d (max 63)", window);
-    hipLaunchKernelGGL(k_sgm_center, dim3(1), dim3(256), 0, to_stream(s), z, H, W, window, out);
-    return sd_check_launch("sd_sgm_center");
+    return sgm_center("sd_sgm_center", 1, z, H, W, window, out, s);
+}
+extern "C" int sd_sgm_center_n(int n, const float* z, int H, int W, int window, float* out, sd_stream s) {
+    return sgm_center("sd_sgm_center_n", n, z, H, W, window, out, s);
 }

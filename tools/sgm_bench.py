@@ -11,7 +11,12 @@ over each stage's time next to the chain's time per step. --mode hh4 / sgbm / hh
 further paths (each one launch that reads C and S and writes S: three volumes, H steps per chain) and times each of
 them alone, with top -> down as an adding pass of the same kernel beside them.
 
+--streams N times, in one session and at the same frame, parameters and protocol, ClassicDepthBatch(N) (N rigs through
+one launch per stage) against N ClassicDepth objects stepped in turn, and the batch's entry points alone (the matcher
+as one stage: its kernels have no batched entry points of their own; a kernel trace of this tool splits it).
+
     python tools/sgm_bench.py --frames 640x480 --num-disparities 128 --block-size 7 --mode hh --json out.json
+    python tools/sgm_bench.py --streams 8 --mode 3way
 """
 
 from __future__ import annotations
@@ -165,6 +170,80 @@ def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str 
     return out
 
 
+def bench_streams(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str, n: int,
+                  batch_only: bool = False) -> dict:
+    """ClassicDepthBatch(n) against n ClassicDepth objects in turn: every stream has frames of its own, the maps and Q
+    are shared. A frame of the batch is step + readout (one sync); the n single objects are timed both with a readout
+    after every step (n syncs, what n independent loops do) and with all steps issued before the n readouts.
+    batch_only leaves the single objects out, so that a kernel trace of the run holds the batch's launches alone."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    scenes = [_scene(np.random.default_rng(i), wc, hc) for i in range(n)]
+    fl = np.stack([sc[0][0] for sc in scenes])
+    fr = np.stack([sc[0][1] for sc in scenes])
+    rect, Q = scenes[0][1], scenes[0][2]
+    kw = dict(rectification=rect, Q=Q, num_disparities=D, block_size=bs, mode=mode, device=dev)
+    out = {"frames": f"{wc}x{hc}", "num_disparities": D, "block_size": bs, "mode": mode, "iters": iters, "warmup": warmup,
+           "streams": n, "workspace_bytes": L.call("sd_sgm_ws_bytes_n", n, hc, wc, D), "clock_mhz_before": clock_probe(dev)}
+    batch = sgm.ClassicDepthBatch(n, **kw)
+    singles = [] if batch_only else [sgm.ClassicDepth(**kw) for _ in range(n)]
+
+    def frame_batch():
+        batch.step(fl, fr).readout()
+
+    def frame_turn():
+        for i, cd in enumerate(singles):
+            cd.step(fl[i], fr[i]).readout()
+
+    def frame_turn_late():
+        res = [cd.step(fl[i], fr[i]) for i, cd in enumerate(singles)]
+        for r in res:
+            r.readout()
+
+    paths = (("batch", frame_batch), ("in_turn", frame_turn), ("in_turn_late_readout", frame_turn_late))
+    for key, fn in paths[:1] if batch_only else paths:
+        ev, wall = _events(fn, iters, warmup)
+        out[key] = {"step_ms_events": ev, "step_ms_wall": wall, "frames_per_s": n / (wall * 1e-3)}
+    if not batch_only:
+        out["speedup_wall"] = out["in_turn"]["step_ms_wall"] / out["batch"]["step_ms_wall"]
+    res = batch.step(fl, fr)
+    torch.cuda.synchronize()
+    q = res.disparity_q4
+    m = batch.matcher
+    out["valid_fraction"] = float((q[:, :, D:] != m.invalid_value).float().mean())
+    if not batch_only:
+        one = singles[0].step(fl[0], fr[0])
+        torch.cuda.synchronize()
+        out["stream0_equals_single"] = bool(torch.equal(q[0], one.disparity_q4))
+
+    # the batch's entry points alone, back-to-back launches on the step's own buffers
+    b, s = batch._buf, L.stream_handle(dev)
+    H, W = hc, wc
+    ws = m.workspace_batch(dev, n, H, W)
+    frames = b["frames"][0]
+    q_tmp = torch.empty_like(q)
+    sw = torch.empty(n * L.call("sd_sgm_speckle_ws_bytes", H, W), dtype=torch.uint8, device=dev)
+    stages = {
+        "rectify (x2)": lambda: [L.call("sd_live_rectify_n", n, frames[i].data_ptr(), H, W, b[f"m1{k}"].data_ptr(),
+                                        b[f"m2{k}"].data_ptr(), 0, b["rect"][i].data_ptr(), s)
+                                 for i, k in enumerate("lr")],
+        "gray (x2)": lambda: [L.call("sd_sgm_gray", b["rect"][i].data_ptr(), n * H, W, b["gray"][i].data_ptr(), s)
+                              for i in range(2)],
+        "matcher": lambda: L.call("sd_sgm_compute_n", n, b["gray"][0].data_ptr(), b["gray"][1].data_ptr(), H, W,
+                                  *m.params(), m.mode_id, ws.data_ptr(), q_tmp.data_ptr(), s),
+        "speckle alone": lambda: (q_tmp.copy_(q), L.call("sd_sgm_speckle_n", n, q_tmp.data_ptr(), H, W, m.invalid_value,
+                                                         m.speckle_window_size, m.speckle_range, sw.data_ptr(), s)),
+        "post": lambda: L.call("sd_sgm_post_n", n, q.data_ptr(), H, W, b["Q"].data_ptr(), b["disp"].data_ptr(),
+                               b["z"].data_ptr(), b["code"].data_ptr(), b["minmax"].data_ptr(), s),
+        "center": lambda: L.call("sd_sgm_center_n", n, b["z"].data_ptr(), H, W, batch.center_window,
+                                 b["center"].data_ptr(), s),
+        "compose": lambda: L.call("sd_live_compose_n", n, b["code"].data_ptr(), b["lut"].data_ptr(), b["vis"].data_ptr(),
+                                  None, None, None, None, None, None, H, W, H, W, 0, s),
+    }
+    out["stage_us"] = {k: 1e3 * _events(fn, iters, warmup)[0] for k, fn in stages.items()}
+    out["clock_mhz_after"] = clock_probe(dev)
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--frames", default="640x480")
@@ -173,11 +252,33 @@ def main() -> None:
     ap.add_argument("--mode", choices=sorted(sgm.MODES), default="3way")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--streams", type=int, default=0,
+                    help="N > 0: ClassicDepthBatch(N) against N ClassicDepth objects in turn")
+    ap.add_argument("--batch-only", action="store_true", help="with --streams: leave the N single objects out")
     ap.add_argument("--json", type=Path, default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sgm_bench needs a HIP device: there is no CPU fallback and no CPU timing")
     w, h = (int(v) for v in args.frames.lower().split("x"))
+    if args.streams:
+        r = bench_streams(w, h, args.num_disparities, args.block_size, args.iters, args.warmup, args.mode, args.streams,
+                          args.batch_only)
+        print(json.dumps(r), flush=True)
+        print(f"\n{r['streams']} streams of {r['frames']}, D = {r['num_disparities']}, bs = {r['block_size']}, mode "
+              f"{r['mode']}; workspace {r['workspace_bytes'] / 1e6:.0f} MB; clock {r['clock_mhz_before']} / "
+              f"{r['clock_mhz_after']} MHz; valid {r['valid_fraction']:.2f}; stream 0 equals the single-stream step: "
+              f"{r.get('stream0_equals_single', 'not compared')}")
+        print("\n| path | ms per step (events) | ms per step (wall) | frames/s |\n|---|---|---|---|")
+        for key in (k for k in ("batch", "in_turn", "in_turn_late_readout") if k in r):
+            v = r[key]
+            print(f"| {key} | {v['step_ms_events']:.3f} | {v['step_ms_wall']:.3f} | {v['frames_per_s']:.0f} |")
+        print("\n| stage of the batch | us |\n|---|---|")
+        for k, us in r["stage_us"].items():
+            print(f"| {k} | {us:.1f} |")
+        if args.json:
+            args.json.parent.mkdir(parents=True, exist_ok=True)
+            args.json.write_text(json.dumps(r, indent=1))
+        return
     r = bench(w, h, args.num_disparities, args.block_size, args.iters, args.warmup, args.mode)
     print(json.dumps(r), flush=True)
     print(f"\nframe {r['frames']}, D = {r['num_disparities']}, bs = {r['block_size']}, mode {r['mode']}: "
