@@ -601,6 +601,31 @@ int sd_sgm_post_n(int n, const int16_t* q, int H, int W, const double* Qdev, flo
 /* sd_sgm_center per stream: z f32 [n][H][W] -> out f32 [n], one block per stream. */
 int sd_sgm_center_n(int n, const float* z, int H, int W, int window, float* out, sd_stream s);
 
+/* ---- per-epoch preview montages of the training CLI (eval_utils.py:42-73: _normalize_map, save_preview_montage) ----
+ * One sample: left | right | gray(target) | gray(pred) along the width, uint8 RGB; each map normalised to the 5th-95th
+ * percentile of its own finite values. Two steps: the percentiles (an exact select, on the device), then the bytes.
+ * Arguments are checked before any launch; no allocation, no synchronisation, graph-capturable; map / sample i of a
+ * batch is byte-identical to a call on it alone. */
+/* np.percentile(v, 100 q) (`linear`) of the FINITE values v of each map, exact: a radix select over full 32-bit keys
+ * (negative: all bits flipped, else the sign bit set), so zeros, -0.0 and negative values are members and order as
+ * numbers (sd_live_select keeps finite values > 0 only, at fixed 2 % / 98 %). values f32 [m][count], 1 <= m <= 64,
+ * 0 <= q_lo <= q_hi <= 1. sel f32 [m][8], row i as sd_live_select_n's: [0] the count n of finite values as uint32;
+ * [1..4] the order statistics at k = floor((n-1) q_lo), min(k+1, n-1), floor((n-1) q_hi) and its successor; [5] lo,
+ * [6] hi = float32(v[k] + (v[k+1] - v[k]) * ((n-1) q - k)) evaluated in fp64. n == 0: NaN in [1..6]. Histogram counts
+ * are 32-bit. work: sd_quantile_select_ws_bytes(m) bytes (-1 for m outside 1..64), zero before the first call; every
+ * call leaves it zero. Six launches. */
+long long sd_quantile_select_ws_bytes(int m);
+int sd_quantile_select_n(int m, const float* values, int count, double q_lo, double q_hi, unsigned* work, float* sel,
+                         sd_stream s);
+/* The montages (:55-73) of n samples (1..64) in one launch: input f32 [n][6][H][W] (planes 0-2 left RGB, 3-5 right RGB),
+ * target, pred f32 [n][H][W], sel_t, sel_p f32 [n][8] (rows of sd_quantile_select_n for target and pred; q 0.05 / 0.95
+ * for the reference's images) -> montage u8 [n][H][4W][3]; H * W need not be a multiple of anything.
+ *   colour  c = trunc(clip(float32(x * 255), 0, 255)), NaN -> 0
+ *   map     vmin = lo, scale = float32(max(fp64(hi) - fp64(lo), 1e-6)); gray = trunc(float32(clip((m - vmin) / scale,
+ *           0, 1) * 255)) in float32, on all three channels; NaN -> 0, +inf -> 255, -inf -> 0; n == 0: all 0 */
+int sd_preview_compose_n(int n, const float* input, const float* target, const float* pred, int H, int W,
+                         const float* sel_t, const float* sel_p, uint8_t* montage, sd_stream s);
+
 #ifdef __cplusplus
 }
 #endif

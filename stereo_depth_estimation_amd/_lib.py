@@ -219,6 +219,10 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_sgm_speckle_n": (_i, [_i, _p, _i, _i, _i, _i, _i, _p, _p]),
     "sd_sgm_post_n": (_i, [_i, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "sd_sgm_center_n": (_i, [_i, _p, _i, _i, _i, _p, _p]),
+    # the epoch preview montages
+    "sd_quantile_select_ws_bytes": (ctypes.c_longlong, [_i]),
+    "sd_quantile_select_n": (_i, [_i, _p, _i, _d, _d, _p, _p, _p]),
+    "sd_preview_compose_n": (_i, [_i, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -22,7 +22,10 @@ checkpoint dict ``{"epoch", "model_state_dict", "optimizer_state_dict", "args", 
   over RCCL (``ddp.DataParallel``); rank 0 writes checkpoints and logs;
 * MLflow is used when importable; otherwise metrics go to ``<run dir>/metrics.jsonl``;
 * ``--device cpu`` and ``--compile`` are rejected: there is no CPU path and no tracing compiler
-  (the reference's CPU path is the parity oracle in ``oracle/``); epoch previews are not written.
+  (the reference's CPU path is the parity oracle in ``oracle/``);
+* the per-epoch preview montages (``train.py:254-289,552-574,640-651``) are composed on the device
+  (:mod:`~stereo_depth_estimation_amd.preview`); ``--preview-samples N`` (new; default 8, the reference's
+  ``MLFLOW_PREVIEW_SAMPLES``) sets their number, 0 turns them off.
 """
 
 from __future__ import annotations
@@ -41,6 +44,7 @@ import torch
 from .dataset import DeviceLoader, FoundationStereoDataset, discover_samples, split_samples
 from .model import StereoUNet
 from .optim import FusedAdamW
+from .preview import log_epoch_previews
 from .train import MLFLOW_TRAIN_LOG_EVERY_BATCHES, run_epoch
 
 
@@ -80,6 +84,14 @@ class TrainConfig:  # reference train.py:38-58, plus the HIP path's options at t
     resume: str | None = None
     precision: str = "fp32"
     sync_bn: bool = False
+    preview_samples: int = 8  # the reference's MLFLOW_PREVIEW_SAMPLES (train.py:24)
+
+
+def _non_negative_int(text: str) -> int:
+    value = int(text)
+    if value < 0:
+        raise argparse.ArgumentTypeError(f"must be >= 0, got {value}")
+    return value
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -120,6 +132,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="fp32: the reference's arithmetic (default); bf16: opt-in fast path (bf16 activations, fp32 accumulation)")
     p.add_argument("--sync-bn", action="store_true",
                    help="multi-GPU: BatchNorm statistics over the global batch (SyncBatchNorm) instead of per rank")
+    p.add_argument("--preview-samples", type=_non_negative_int, default=8,
+                   help="fixed validation samples written as preview montages after every epoch (0: none)")
     return p
 
 
@@ -286,6 +300,18 @@ def main(argv=None) -> dict:
     val_loader = (DeviceLoader(val_ds, args.batch_size, shuffle=False, num_workers=args.num_workers, device=device,
                                persistent_workers=persistent, sampler=val_sampler) if val_ds is not None else None)
 
+    # the fixed preview samples (train.py:552-574), on rank 0. The loader has a generator of its own: a DataLoader
+    # iterator draws its base seed from its generator or, without one, from the global RNG, which previews must not touch
+    preview_source = val_samples if val_samples else train_samples
+    preview_count = min(args.preview_samples, len(preview_source))
+    preview_loader = None
+    if preview_count > 0 and rank == 0:
+        preview_ds = FoundationStereoDataset(preview_source[:preview_count], image_size=image_size,
+                                             cache_root=args.cache_root, require_cache=args.require_cache)
+        preview_loader = DeviceLoader(preview_ds, min(args.batch_size, preview_count), shuffle=False, num_workers=0,
+                                      device=device, generator=torch.Generator().manual_seed(args.seed))
+        print(f"MLflow previews: logging {preview_count} fixed {'val' if val_samples else 'train'} samples each epoch.")
+
     model = StereoUNet(in_channels=6, out_channels=1, precision=args.precision).to(device)
     optimizer = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
     start_epoch, global_step, best_val_mae, best_epoch = 1, 0, float("inf"), -1
@@ -319,8 +345,11 @@ def main(argv=None) -> dict:
     else:
         output_dir = Path(args.output_dir).expanduser().resolve() / run_id
     checkpoints_dir = output_dir / "checkpoints"
+    preview_root = output_dir / "mlflow_previews"
     if rank == 0:
         checkpoints_dir.mkdir(parents=True, exist_ok=True)
+        if preview_loader is not None:
+            preview_root.mkdir(parents=True, exist_ok=True)
         (output_dir / "config.json").write_text(json.dumps(asdict(args), indent=2), encoding="utf-8")
         if mlflow is None:
             logger = _JsonlLogger(output_dir / "metrics.jsonl")
@@ -345,6 +374,11 @@ def main(argv=None) -> dict:
                 best_val_mae, best_epoch = candidate, epoch
             if rank == 0:
                 logger.log_metrics(metrics, step=epoch)
+                if preview_loader is not None:  # train.py:640-651: after the epoch metrics, before the checkpoints
+                    log_epoch_previews(model, preview_loader, device, epoch, preview_root)
+                    if mlflow is not None:
+                        mlflow.log_artifacts(str(preview_root / f"epoch_{epoch:04d}"),
+                                             artifact_path=f"previews/epoch_{epoch:04d}")
                 kw = dict(global_step=global_step, best_val_mae=best_val_mae, best_epoch=best_epoch)
                 save_checkpoint(checkpoints_dir / "last.pt", epoch, model, optimizer, args, metrics, **kw)
                 if improved:
