@@ -204,6 +204,15 @@ int sd_wgrad_reduce_batch(const sd_wred_job* jobs, int njobs, sd_stream s);
 int sd_read_cache_batch(const char* const* paths, int n, int H, int W, uint8_t* left, uint8_t* right,
                         uint16_t* disparity, int threads, char* err, int errlen);
 
+/* Writes n cache files in that format from host buffers left/right [n][H][W][3], disp_f16 [n][H][W] with at most
+ * min(threads, 16) host threads: a zip of left.npy, right.npy, disparity.npy (version-1.0 .npy headers, C order), members
+ * stored (compress == 0, np.savez) or raw-deflated (np.savez_compressed). Each file is written under a temporary name
+ * in its own directory (which must exist) and renamed over the target, so a target is either absent, its earlier self
+ * or complete. Returns 0, or 1 + the index of the first path that failed (path and reason in err; its temporary file
+ * removed, an earlier file at the target untouched; the other files are still written), or -1 for bad args. */
+int sd_write_cache_batch(const char* const* paths, int n, int H, int W, const uint8_t* left, const uint8_t* right,
+                         const uint16_t* disp_f16, int compress, int threads, char* err, int errlen);
+
 /* PNG frames of the un-cached source (reference dataset.py:23-30,184-212: PIL open + convert("RGB")): 8-bit RGB or
  * RGBA, not interlaced. sd_png_size reads the IHDR; sd_read_png_batch decodes n frames of H x W with `threads` host
  * threads into out [n][H][W][3]. Returns as sd_read_cache_batch (other PNG kinds: an error, for a PIL fallback). */
@@ -389,6 +398,15 @@ int sd_stereo_preprocess(const uint8_t* left, const uint8_t* right, const uint8_
  * f16 [B][Ho][Wo] already at the training resolution -> the same three outputs. */
 int sd_stereo_from_cache(const uint8_t* left, const uint8_t* right, const uint16_t* disp_f16, int batch, int Ho,
                          int Wo, float* input, float* target, uint8_t* valid, sd_stream s);
+/* The cache builder's kernel (reference cache.py:50-112 + save_cached_sample, dataset.py:110-128): the inputs of
+ * sd_stereo_preprocess -> the cache's own layout, out_left/out_right uint8 [B][Ho][Wo][3] and out_disp_f16 f16 bits
+ * [B][Ho][Wo], i.e. the buffers sd_read_cache_batch fills and sd_stereo_from_cache consumes. Per pixel the fp32 values
+ * are those of sd_stereo_preprocess (the same device code); colour = (uint8) clip(x * 255, 0, 255) truncated,
+ * disparity = float16(target), round to nearest even (subnormals kept, overflow to inf). Four pixels per thread with
+ * word stores when Wo % 4 == 0, out_left/out_right are 4-B and out_disp_f16 is 8-B aligned; a per-pixel form otherwise.
+ * Allocates nothing, does not synchronise. */
+int sd_stereo_to_cache(const uint8_t* left, const uint8_t* right, const uint8_t* disp_rgb, int batch, int Hs, int Ws,
+                       int Ho, int Wo, uint8_t* out_left, uint8_t* out_right, uint16_t* out_disp_f16, sd_stream s);
 /* Asymmetric colour augmentation (FoundationStereoDataset._augment_rgb, dataset.py:248-270, torchvision 0.25
  * functional ops), in place on input [B][6][H][W] f32 = 2B RGB images (left, right of each pair).
  * params [2B][7] f32 per image: brightness, contrast, saturation factors, hue shift, gamma, blur sigma

@@ -150,6 +150,7 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_bn_bwd_reduce": (_i, [_i, _p, _p, _p, _p, _p, _p, _i64, _i, _p, _p]),
     "sd_bn_bwd_finalize": (_i, [_p, _i, _i, _d, _p, _p, _i, _p, _p, _p, _p]),
     "sd_read_cache_batch": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, ctypes.c_char_p, _i]),
+    "sd_write_cache_batch": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, ctypes.c_char_p, _i]),
     "sd_png_size": (_i, [ctypes.c_char_p, _p, _p]),
     "sd_read_png_batch": (_i, [_p, _i, _i, _i, _p, _i, ctypes.c_char_p, _i]),
     "sd_bn_rows_sum64": (_i, [_p, _i, _i, _d, _p, _p]),
@@ -181,6 +182,7 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_resize_bilinear": (_i, [_p, _i, _i, _i, _p, _i, _i, _f, _p]),
     "sd_stereo_preprocess": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "sd_stereo_from_cache": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "sd_stereo_to_cache": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "sd_augment_rgb": (_i, [_p, _i, _i, _i, _p, _i, ctypes.c_uint64, _p, _p]),
     "sd_live_frontend": (_i, [_i, _p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _i, _i, _p]),
     "sd_live_rectify": (_i, [_p, _i, _i, _p, _p, _p, _p]),

@@ -1,4 +1,4 @@
-// Native host readers for the data path: the reference's sample cache and its PNG frames.
+// Native host readers for the data path: the reference's sample cache and its PNG frames; and the cache's writer.
 // Sample cache (reference dataset.py:86-105 load_cached_sample, cache.py:50-112):
 // one np.savez file per pair, a zip of left.npy / right.npy (uint8 HWC) and disparity.npy (f16 HW): stored members
 // (np.savez, the default) or raw-deflate members (np.savez_compressed, the reference's `cache.py --compress`).
@@ -11,6 +11,7 @@
 #include <zlib.h>
 
 #include <atomic>
+#include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -192,6 +193,228 @@ extern "C" int sd_read_cache_batch(const char* const* paths, int n, int H, int W
         for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
             bool ok = paths[i] && read_file(paths[i], buf, why);
             if (ok) ok = parse_npz(buf, H, W, left + i * rgb, right + i * rgb, disparity + i * hw, scratch, why);
+            if (!ok) {
+                std::lock_guard<std::mutex> g(mu);
+                if (i < first_bad.load()) {
+                    first_bad.store(i);
+                    bad_why = why;
+                }
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    const int bad = first_bad.load();
+    if (bad < n) {
+        if (err && errlen > 0)
+            snprintf(err, (size_t)errlen, "%s: %s", paths[bad] ? paths[bad] : "(null)", bad_why.c_str());
+        return bad + 1;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------ the cache writer
+// save_cached_sample's file (reference dataset.py:110-128: np.savez / np.savez_compressed of left, right, disparity)
+// written from the buffers the device filled: the three .npy members (version 1.0 headers, padded as NumPy pads them)
+// in a plain zip, the whole file composed in memory, written under a temporary name beside its target and renamed over
+// it. The reference writes in place, so a build that is interrupted leaves a truncated entry that its next run skips as
+// existing; here the target is never a partial file.
+
+namespace {
+
+void put16(std::vector<unsigned char>& o, uint32_t v) {
+    o.push_back((unsigned char)v);
+    o.push_back((unsigned char)(v >> 8));
+}
+void put32(std::vector<unsigned char>& o, uint32_t v) {
+    put16(o, v & 0xffffu);
+    put16(o, v >> 16);
+}
+
+// magic, version 1.0, header length, then the dict text space-padded so that the data starts at a multiple of 64
+// (numpy.lib.format._wrap_header, ARRAY_ALIGN = 64), ending in '\n'
+void npy_member(std::vector<unsigned char>& o, const char* descr, const std::string& shape, const void* data,
+                size_t bytes) {
+    std::string hdr = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape + ", }";
+    const size_t pad = 64 - (10 + hdr.size() + 1) % 64;
+    hdr.append(pad, ' ');  // 1..64, as NumPy: a full 64 when the text already ends on the boundary
+    hdr.push_back('\n');
+    o.clear();
+    o.reserve(10 + hdr.size() + bytes);
+    o.insert(o.end(), {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0});
+    put16(o, (uint32_t)hdr.size());
+    o.insert(o.end(), hdr.begin(), hdr.end());
+    const unsigned char* p = static_cast<const unsigned char*>(data);
+    o.insert(o.end(), p, p + bytes);
+}
+
+bool deflate_member(const std::vector<unsigned char>& in, std::vector<unsigned char>& out, std::string& why) {
+    z_stream zs;
+    memset(&zs, 0, sizeof(zs));
+    if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -MAX_WBITS, 8, Z_DEFAULT_STRATEGY) != Z_OK) {
+        why = "deflateInit2 failed";
+        return false;
+    }
+    out.resize(deflateBound(&zs, (uLong)in.size()));
+    zs.next_in = const_cast<unsigned char*>(in.data());
+    zs.avail_in = (uInt)in.size();
+    zs.next_out = out.data();
+    zs.avail_out = (uInt)out.size();
+    const int rc = deflate(&zs, Z_FINISH);
+    out.resize(zs.total_out);
+    deflateEnd(&zs);
+    if (rc != Z_STREAM_END) {
+        why = "deflate failed";
+        return false;
+    }
+    return true;
+}
+
+// the zip of one sample in `file` (local header + data per member, central directory, end record); no zip64: a
+// member of 4 GiB or more is refused
+bool compose_npz(int H, int W, const uint8_t* left, const uint8_t* right, const uint16_t* disp, bool compress,
+                 std::vector<unsigned char>& file, std::vector<unsigned char>& member, std::vector<unsigned char>& packed,
+                 std::string& why) {
+    const std::string s3 = "(" + std::to_string(H) + ", " + std::to_string(W) + ", 3)";
+    const std::string s2 = "(" + std::to_string(H) + ", " + std::to_string(W) + ")";
+    const size_t rgb = (size_t)H * W * 3, dbytes = (size_t)H * W * 2;
+    if (rgb + 4096 >= 0xffffffffull / 3) {
+        why = "sample too large for a zip without zip64";
+        return false;
+    }
+    struct Entry {
+        const char* name;
+        uint32_t crc, csize, usize, offset;
+    } ent[3] = {{"left.npy", 0, 0, 0, 0}, {"right.npy", 0, 0, 0, 0}, {"disparity.npy", 0, 0, 0, 0}};
+    const uint32_t method = compress ? 8 : 0;
+    const uint32_t dos_time = 0, dos_date = 0x21;  // 1980-01-01 00:00: the contents, not the clock, define an entry
+    file.clear();
+    for (int m = 0; m < 3; ++m) {
+        if (m < 2)
+            npy_member(member, "|u1", s3, m == 0 ? left : right, rgb);
+        else
+            npy_member(member, "<f2", s2, disp, dbytes);
+        const std::vector<unsigned char>* body = &member;
+        if (compress) {
+            if (!deflate_member(member, packed, why)) return false;
+            body = &packed;
+        }
+        Entry& e = ent[m];
+        e.crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), member.data(), (uInt)member.size());
+        e.usize = (uint32_t)member.size();
+        e.csize = (uint32_t)body->size();
+        e.offset = (uint32_t)file.size();
+        const size_t nlen = strlen(e.name);
+        put32(file, 0x04034b50u);
+        put16(file, 20);  // version needed: 2.0 (deflate)
+        put16(file, 0);   // flags: sizes and CRC in this header, no data descriptor
+        put16(file, method);
+        put16(file, dos_time);
+        put16(file, dos_date);
+        put32(file, e.crc);
+        put32(file, e.csize);
+        put32(file, e.usize);
+        put16(file, (uint32_t)nlen);
+        put16(file, 0);
+        file.insert(file.end(), e.name, e.name + nlen);
+        file.insert(file.end(), body->begin(), body->end());
+    }
+    const uint32_t cd_off = (uint32_t)file.size();
+    for (const Entry& e : ent) {
+        const size_t nlen = strlen(e.name);
+        put32(file, 0x02014b50u);
+        put16(file, 3u << 8 | 20);  // made by: unix, 2.0
+        put16(file, 20);
+        put16(file, 0);
+        put16(file, method);
+        put16(file, dos_time);
+        put16(file, dos_date);
+        put32(file, e.crc);
+        put32(file, e.csize);
+        put32(file, e.usize);
+        put16(file, (uint32_t)nlen);
+        put16(file, 0);  // extra
+        put16(file, 0);  // comment
+        put16(file, 0);  // disk
+        put16(file, 0);  // internal attributes
+        put32(file, 0100644u << 16);
+        put32(file, e.offset);
+        file.insert(file.end(), e.name, e.name + nlen);
+    }
+    const uint32_t cd_size = (uint32_t)file.size() - cd_off;
+    put32(file, 0x06054b50u);
+    put16(file, 0);
+    put16(file, 0);
+    put16(file, 3);
+    put16(file, 3);
+    put32(file, cd_size);
+    put32(file, cd_off);
+    put16(file, 0);
+    return true;
+}
+
+std::atomic<unsigned> g_tmp_serial{0};
+
+// `file` at `path`, by way of a temporary file in the same directory and rename(2)
+bool write_atomic(const char* path, const std::vector<unsigned char>& file, std::string& why) {
+    const std::string tmp = std::string(path) + ".tmp." + std::to_string((long)getpid()) + "." +
+                            std::to_string(g_tmp_serial.fetch_add(1));
+    const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0666);
+    if (fd < 0) {
+        why = std::string("cannot create the temporary file (") + strerror(errno) + ")";
+        return false;
+    }
+    size_t put = 0;
+    bool ok = true;
+    while (put < file.size()) {
+        const ssize_t r = write(fd, file.data() + put, file.size() - put);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) {
+            why = std::string("write failed (") + strerror(errno) + ")";
+            ok = false;
+            break;
+        }
+        put += (size_t)r;
+    }
+    if (close(fd) != 0 && ok) {
+        why = std::string("close failed (") + strerror(errno) + ")";
+        ok = false;
+    }
+    if (ok && rename(tmp.c_str(), path) != 0) {
+        why = std::string("cannot rename over the target (") + strerror(errno) + ")";
+        ok = false;
+    }
+    if (!ok) unlink(tmp.c_str());
+    return ok;
+}
+
+}  // namespace
+
+extern "C" int sd_write_cache_batch(const char* const* paths, int n, int H, int W, const uint8_t* left,
+                                    const uint8_t* right, const uint16_t* disp_f16, int compress, int threads, char* err,
+                                    int errlen) {
+    if (!paths || n < 0 || H <= 0 || W <= 0 || !left || !right || !disp_f16) {
+        if (err && errlen > 0) snprintf(err, (size_t)errlen, "sd_write_cache_batch: bad args");
+        return -1;
+    }
+    if (threads > 16) threads = 16;  // a fixed ceiling, not the machine's CPU count
+    if (threads < 1) threads = 1;
+    if (threads > n) threads = n > 0 ? n : 1;
+    const size_t rgb = (size_t)H * W * 3, hw = (size_t)H * W;
+    std::atomic<int> next{0}, first_bad{n};
+    std::mutex mu;
+    std::string bad_why;
+    auto work = [&]() {
+        std::vector<unsigned char> file, member, packed;
+        std::string why;
+        for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
+            bool ok = paths[i] != nullptr;
+            if (!ok) why = "null path";
+            if (ok) ok = compose_npz(H, W, left + i * rgb, right + i * rgb, disp_f16 + i * hw, compress != 0, file, member,
+                                     packed, why);
+            if (ok) ok = write_atomic(paths[i], file, why);
             if (!ok) {
                 std::lock_guard<std::mutex> g(mu);
                 if (i < first_bad.load()) {

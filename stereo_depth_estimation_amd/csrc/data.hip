@@ -21,6 +21,18 @@ __device__ __forceinline__ float decode_rgb24(const uint8_t* px) {
     return (float)((int)px[0] * 65025 + (int)px[1] * 255 + (int)px[2]) / 1000.f;
 }
 
+// The fp32 value of one output pixel from its four taps (top-left, top-right, bottom-left, bottom-right): one colour
+// channel, and the disparity target. k_stereo_preprocess and the cache kernels below all take their values from these
+// two functions, so a cache entry holds exactly the sample the training path computes.
+__device__ __forceinline__ float rgb_sample(uint8_t a, uint8_t b, uint8_t c, uint8_t d, float lx, float ly) {
+    return bilerp((float)a / 255.f, (float)b / 255.f, (float)c / 255.f, (float)d / 255.f, lx, ly);
+}
+
+__device__ __forceinline__ float disp_sample(const uint8_t* a, const uint8_t* b, const uint8_t* c, const uint8_t* d,
+                                             float lx, float ly, float wscale) {
+    return bilerp(decode_rgb24(a), decode_rgb24(b), decode_rgb24(c), decode_rgb24(d), lx, ly) * wscale;
+}
+
 __global__ void k_stereo_preprocess(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
                                     const uint8_t* __restrict__ disp, int B, int Hs, int Ws, int Ho, int Wo,
                                     float wscale, float* __restrict__ input, float* __restrict__ target,
@@ -40,15 +52,140 @@ __global__ void k_stereo_preprocess(const uint8_t* __restrict__ left, const uint
         float* in_b = input + (size_t)b * 6 * plane + rem;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            in_b[c * plane] = bilerp((float)left[o00 + c] / 255.f, (float)left[o01 + c] / 255.f,
-                                     (float)left[o10 + c] / 255.f, (float)left[o11 + c] / 255.f, lx, ly);
-            in_b[(3 + c) * plane] = bilerp((float)right[o00 + c] / 255.f, (float)right[o01 + c] / 255.f,
-                                           (float)right[o10 + c] / 255.f, (float)right[o11 + c] / 255.f, lx, ly);
+            in_b[c * plane] = rgb_sample(left[o00 + c], left[o01 + c], left[o10 + c], left[o11 + c], lx, ly);
+            in_b[(3 + c) * plane] = rgb_sample(right[o00 + c], right[o01 + c], right[o10 + c], right[o11 + c], lx, ly);
         }
-        const float t = bilerp(decode_rgb24(disp + o00), decode_rgb24(disp + o01), decode_rgb24(disp + o10),
-                               decode_rgb24(disp + o11), lx, ly) * wscale;
+        const float t = disp_sample(disp + o00, disp + o01, disp + o10, disp + o11, lx, ly, wscale);
         target[e] = t;
         valid[e] = t > 0.f;
+    }
+}
+
+// ---- source frames -> the sample cache's own bytes (reference save_cached_sample, dataset.py:110-128, on the values
+// above): colour = (uint8) clip(x * 255, 0, 255), truncated; disparity = float16(t), round to nearest even (the
+// hardware conversion: subnormal results kept, overflow to inf, as ndarray.astype(np.float16)).
+// The conversions start from the fp32 value as k_stereo_preprocess stores it. Without the (empty) asm the compiler may
+// fold the sample's last multiply into the conversion: v_fma_mixlo_f16 rounds the exact product once, to float16,
+// where the cache holds float16(float32(product)); seen as one differing bit in a few thousand values.
+__device__ __forceinline__ float as_stored_f32(float x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ uint32_t cache_byte(float x) {
+    return (uint32_t)(int)fminf(fmaxf(as_stored_f32(x) * 255.0f, 0.f), 255.f);
+}
+__device__ __forceinline__ uint16_t cache_half(float t) { return __half_as_ushort(__float2half_rn(as_stored_f32(t))); }
+
+// The RGB triplets of the two horizontally neighbouring taps of one source row: x1 is x0 + 1, or x0 at the right edge.
+// In the first case the six bytes are contiguous and are copied as a 4-B and a 2-B piece of no particular alignment,
+// which the compiler turns into one dword and one short load (gfx950 reads global memory at any alignment) in place
+// of six byte loads; exactly the bytes of the two taps are read, nothing past them.
+struct TapPair {
+    uint8_t a[3], b[3];
+};
+__device__ __forceinline__ TapPair load_tap_pair(const uint8_t* row, int x0, int x1) {
+    const uint8_t* p = row + x0 * 3;
+    TapPair t;
+    if (x1 != x0) {
+        uint32_t w;
+        uint16_t h;
+        __builtin_memcpy(&w, p, 4);
+        __builtin_memcpy(&h, p + 4, 2);
+        t.a[0] = (uint8_t)w, t.a[1] = (uint8_t)(w >> 8), t.a[2] = (uint8_t)(w >> 16);
+        t.b[0] = (uint8_t)(w >> 24), t.b[1] = (uint8_t)h, t.b[2] = (uint8_t)(h >> 8);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t.a[c] = t.b[c] = p[c];
+    }
+    return t;
+}
+
+// one output pixel per thread, byte and half stores: any width, any alignment
+__global__ void k_stereo_to_cache(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                  const uint8_t* __restrict__ disp, int B, int Hs, int Ws, int Ho, int Wo, float wscale,
+                                  uint8_t* __restrict__ out_left, uint8_t* __restrict__ out_right,
+                                  uint16_t* __restrict__ out_disp) {
+    const long long plane = (long long)Ho * Wo, total = (long long)B * plane;
+    for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int b = (int)(e / plane);
+        const int rem = (int)(e - (long long)b * plane);
+        const int y = rem / Wo, x = rem - y * Wo;
+        int y0, y1, x0, x1;
+        float ly, lx;
+        src_index(y, Ho, Hs, y0, y1, ly);
+        src_index(x, Wo, Ws, x0, x1, lx);
+        const size_t img = (size_t)b * Hs * Ws * 3;
+        const size_t r0 = img + (size_t)y0 * Ws * 3, r1 = img + (size_t)y1 * Ws * 3;
+        const size_t px = (size_t)e * 3;
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            const uint8_t* src = side ? right : left;
+            uint8_t* dst = (side ? out_right : out_left) + px;
+            const TapPair top = load_tap_pair(src + r0, x0, x1), bot = load_tap_pair(src + r1, x0, x1);
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                dst[c] = (uint8_t)cache_byte(rgb_sample(top.a[c], top.b[c], bot.a[c], bot.b[c], lx, ly));
+        }
+        const TapPair top = load_tap_pair(disp + r0, x0, x1), bot = load_tap_pair(disp + r1, x0, x1);
+        out_disp[e] = cache_half(disp_sample(top.a, top.b, bot.a, bot.b, lx, ly, wscale));
+    }
+}
+
+// Four output pixels of one row per thread (Wo % 4 == 0, outputs 4- and 8-B aligned): the 12 packed HWC bytes of each
+// side leave as three 4-B words and the four halves as one 8-B store, where the per-pixel form issues 24 byte and 4
+// half stores; the row indices and the vertical weight are computed once for the four pixels, and the taps of the two
+// source rows are gathered once per image (16 tap pairs) and feed all three channels' arithmetic from registers.
+// 87 VGPRs, no scratch, 5 waves per SIMD (the per-pixel form: 38 VGPRs, 8 waves).
+// Measured (tools/cache_bench.py kernel arm; B = 64 -> 240x320, device events): the store count does NOT
+// decide this kernel. From 960x540 this form takes 101 us and the per-pixel form 80 us; from 640x480 83 / 70, from
+// 320x240 79 / 71, from 160x120 80 / 71. The time hardly follows the bytes (299 MB to 11 MB of source): with 28
+// correctly rounded fp32 divisions per pixel (the /255 and /1000 of the reference's order, ~10 VALU instructions each)
+// the work is VALU-bound, not HBM-bound, and the wider stores buy nothing against the lower occupancy and the 4x
+// larger lane stride of the loads. The form is kept as the dispatch for aligned, Wo % 4 == 0 outputs; beside 70 ms
+// of PNG inflation per batch the difference is 0.02 % of a build. Not tried: a 256-entry table of b / 255.f in LDS.
+__global__ void k_stereo_to_cache4(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                   const uint8_t* __restrict__ disp, int B, int Hs, int Ws, int Ho, int Wo,
+                                   float wscale, uint8_t* __restrict__ out_left, uint8_t* __restrict__ out_right,
+                                   uint16_t* __restrict__ out_disp) {
+    const long long plane = (long long)Ho * Wo, total4 = (long long)B * plane / 4;
+    for (long long q = blockIdx.x * 256LL + threadIdx.x; q < total4; q += (long long)gridDim.x * 256) {
+        const long long e = q * 4;
+        const int b = (int)(e / plane);
+        const int rem = (int)(e - (long long)b * plane);
+        const int y = rem / Wo, x = rem - y * Wo;  // x % 4 == 0: the four pixels share the row
+        int y0, y1, x0[4], x1[4];
+        float ly, lx[4];
+        src_index(y, Ho, Hs, y0, y1, ly);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) src_index(x + p, Wo, Ws, x0[p], x1[p], lx[p]);
+        const size_t img = (size_t)b * Hs * Ws * 3;
+        const size_t r0 = img + (size_t)y0 * Ws * 3, r1 = img + (size_t)y1 * Ws * 3;
+#pragma unroll 1  // one image's taps in registers at a time
+        for (int side = 0; side < 2; ++side) {
+            const uint8_t* src = side ? right : left;
+            TapPair top[4], bot[4];  // the taps of the two source rows, gathered once for the three channels
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                top[p] = load_tap_pair(src + r0, x0[p], x1[p]);
+                bot[p] = load_tap_pair(src + r1, x0[p], x1[p]);
+            }
+            uint32_t v[12];  // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    v[p * 3 + c] = cache_byte(rgb_sample(top[p].a[c], top[p].b[c], bot[p].a[c], bot[p].b[c], lx[p], ly));
+            uint32_t* dst = reinterpret_cast<uint32_t*>((side ? out_right : out_left) + (size_t)e * 3);
+#pragma unroll
+            for (int w = 0; w < 3; ++w) dst[w] = v[4 * w] | v[4 * w + 1] << 8 | v[4 * w + 2] << 16 | v[4 * w + 3] << 24;
+        }
+        uint32_t h[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const TapPair top = load_tap_pair(disp + r0, x0[p], x1[p]), bot = load_tap_pair(disp + r1, x0[p], x1[p]);
+            h[p] = cache_half(disp_sample(top.a, top.b, bot.a, bot.b, lx[p], ly, wscale));
+        }
+        *reinterpret_cast<uint2*>(out_disp + e) = make_uint2(h[0] | h[1] << 16, h[2] | h[3] << 16);
     }
 }
 
@@ -139,6 +276,24 @@ extern "C" int sd_stereo_from_cache(const uint8_t* left, const uint8_t* right, c
         hipLaunchKernelGGL(k_stereo_from_cache, dim3(grid_for((long long)batch * Ho * Wo)), dim3(256), 0, to_stream(s),
                            left, right, reinterpret_cast<const __half*>(disp_f16), batch, Ho, Wo, input, target, valid);
     return sd_check_launch("sd_stereo_from_cache");
+}
+
+extern "C" int sd_stereo_to_cache(const uint8_t* left, const uint8_t* right, const uint8_t* disp_rgb, int batch, int Hs,
+                                  int Ws, int Ho, int Wo, uint8_t* out_left, uint8_t* out_right,
+                                  uint16_t* out_disp_f16, sd_stream s) {
+    SD_REQUIRE(left && right && disp_rgb && out_left && out_right && out_disp_f16, "sd_stereo_to_cache: null pointer");
+    SD_REQUIRE(batch > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "sd_stereo_to_cache: bad sizes");
+    const float wscale = (float)((double)Wo / (double)Ws);  // as sd_stereo_preprocess
+    const bool vec = Wo % 4 == 0 && (uintptr_t)out_left % 4 == 0 && (uintptr_t)out_right % 4 == 0 &&
+                     (uintptr_t)out_disp_f16 % 8 == 0;
+    if (vec)
+        hipLaunchKernelGGL(k_stereo_to_cache4, dim3(grid_for((long long)batch * Ho * Wo / 4)), dim3(256), 0,
+                           to_stream(s), left, right, disp_rgb, batch, Hs, Ws, Ho, Wo, wscale, out_left, out_right,
+                           out_disp_f16);
+    else
+        hipLaunchKernelGGL(k_stereo_to_cache, dim3(grid_for((long long)batch * Ho * Wo)), dim3(256), 0, to_stream(s),
+                           left, right, disp_rgb, batch, Hs, Ws, Ho, Wo, wscale, out_left, out_right, out_disp_f16);
+    return sd_check_launch("sd_stereo_to_cache");
 }
 
 // =====================================================================================

@@ -300,6 +300,27 @@ def read_cache_batch(paths, image_size: tuple[int, int], left: torch.Tensor, rig
         raise ValueError(f"Cache entry is invalid or shape-mismatched: {msg}")
 
 
+def write_cache_batch(paths, image_size: tuple[int, int], left: torch.Tensor, right: torch.Tensor, disparity: torch.Tensor,
+                      compress: bool = False, threads: int = 16) -> None:
+    """Native (``sd_write_cache_batch``) write of reference-format cache files (``save_cached_sample``, reference
+    ``dataset.py:110-128``) from host tensors in ``read_cache_batch``'s layout. Each file appears under its name
+    complete or not at all (temporary file + rename); the parent directories must exist. OSError names the first
+    path that failed."""
+    H, W = image_size
+    n = len(paths)
+    for t, shape, dt in ((left, (n, H, W, 3), torch.uint8), (right, (n, H, W, 3), torch.uint8),
+                         (disparity, (n, H, W), torch.int16)):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device.type != "cpu":
+            raise ValueError(f"write_cache_batch: expected a contiguous CPU {dt} tensor of {shape}, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(str(p)) for p in paths])
+    err = ctypes.create_string_buffer(1024)
+    rc = L.load().sd_write_cache_batch(ctypes.cast(arr, ctypes.c_void_p), n, H, W, left.data_ptr(), right.data_ptr(),
+                                       disparity.data_ptr(), int(bool(compress)), threads, err, len(err))
+    if rc != 0:
+        raise OSError(f"Cache entry could not be written: {err.value.decode(errors='replace')}")
+
+
 def read_png_batch(paths, size: tuple[int, int], out: torch.Tensor, threads: int = 16) -> bool:
     """Native (``sd_read_png_batch``) decode of n PNG frames of one source size into a uint8 [n,H,W,3] host tensor,
     as ``read_rgb_uint8`` (PIL ``convert("RGB")``) returns them. False when a file is not an 8-bit RGB/RGBA,
