@@ -225,6 +225,10 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_quantile_select_ws_bytes": (ctypes.c_longlong, [_i]),
     "sd_quantile_select_n": (_i, [_i, _p, _i, _d, _d, _p, _p, _p]),
     "sd_preview_compose_n": (_i, [_i, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    # predict and evaluate from files: the output stage and the PNG writer
+    "sd_disp_export_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
+    "sd_disp_export": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "sd_write_png_batch": (_i, [_p, _i, _i, _i, _p, _i, _i, ctypes.c_char_p, _i]),
 }
 
 _lib = None

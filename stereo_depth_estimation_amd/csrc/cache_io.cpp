@@ -1,4 +1,5 @@
-// Native host readers for the data path: the reference's sample cache and its PNG frames; and the cache's writer.
+// Native host readers for the data path: the reference's sample cache and its PNG frames; the cache's writer; and the
+// PNG writer of the predict tool (at the end of the file).
 // Sample cache (reference dataset.py:86-105 load_cached_sample, cache.py:50-112):
 // one np.savez file per pair, a zip of left.npy / right.npy (uint8 HWC) and disparity.npy (f16 HW): stored members
 // (np.savez, the default) or raw-deflate members (np.savez_compressed, the reference's `cache.py --compress`).
@@ -549,6 +550,134 @@ extern "C" int sd_read_png_batch(const char* const* paths, int n, int H, int W, 
         for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
             bool ok = paths[i] && read_file(paths[i], buf, why);
             if (ok) ok = decode_png(buf, H, W, out + (size_t)i * H * W * 3, z, raw, why);
+            if (!ok) {
+                std::lock_guard<std::mutex> g(mu);
+                if (i < first_bad.load()) {
+                    first_bad.store(i);
+                    bad_why = why;
+                }
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    const int bad = first_bad.load();
+    if (bad < n) {
+        if (err && errlen > 0)
+            snprintf(err, (size_t)errlen, "%s: %s", paths[bad] ? paths[bad] : "(null)", bad_why.c_str());
+        return bad + 1;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------ the PNG writer (disparity files of predict.py)
+// n RGB images from the buffers the device filled -> 8-bit RGB PNGs a reader of the dataset's disparity files takes
+// (sd_read_png_batch, PIL, the reference's loader): not interlaced, filter type 0 on every row (the codes of a disparity
+// image are no smoother after a filter, and the choice costs a pass), one zlib stream in one IDAT chunk. Composed in
+// memory and written through write_atomic, so a target is never a partial file.
+
+namespace {
+
+void put_be32(std::vector<unsigned char>& o, uint32_t v) {
+    o.push_back((unsigned char)(v >> 24));
+    o.push_back((unsigned char)(v >> 16));
+    o.push_back((unsigned char)(v >> 8));
+    o.push_back((unsigned char)v);
+}
+
+// length, type, data, CRC over type + data; `o` already ends with the data of `len` bytes after the 8-byte head at `at`
+void close_chunk(std::vector<unsigned char>& o, size_t at) {
+    const size_t len = o.size() - at - 8;
+    o[at] = (unsigned char)(len >> 24), o[at + 1] = (unsigned char)(len >> 16);
+    o[at + 2] = (unsigned char)(len >> 8), o[at + 3] = (unsigned char)len;
+    uLong crc = crc32(0L, Z_NULL, 0);
+    for (size_t pos = at + 4; pos < o.size();) {  // crc32 takes a uInt length
+        const size_t step = o.size() - pos < ((size_t)1 << 30) ? o.size() - pos : ((size_t)1 << 30);
+        crc = crc32(crc, o.data() + pos, (uInt)step);
+        pos += step;
+    }
+    put_be32(o, (uint32_t)crc);
+}
+size_t open_chunk(std::vector<unsigned char>& o, const char* type) {
+    const size_t at = o.size();
+    put_be32(o, 0);
+    o.insert(o.end(), type, type + 4);
+    return at;
+}
+
+bool compose_png(int H, int W, const uint8_t* rgb, int level, std::vector<unsigned char>& file,
+                 std::vector<unsigned char>& raw, std::string& why) {
+    const size_t stride = (size_t)W * 3;
+    if ((stride + 1) * (size_t)H >= ((size_t)1 << 31)) {
+        why = "image too large for one IDAT chunk";
+        return false;
+    }
+    raw.resize((stride + 1) * (size_t)H);
+    for (int y = 0; y < H; ++y) {
+        unsigned char* row = &raw[(size_t)y * (stride + 1)];
+        row[0] = 0;  // filter type 0: None
+        memcpy(row + 1, rgb + (size_t)y * stride, stride);
+    }
+    static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    file.clear();
+    file.insert(file.end(), sig, sig + 8);
+    size_t at = open_chunk(file, "IHDR");
+    put_be32(file, (uint32_t)W);
+    put_be32(file, (uint32_t)H);
+    file.insert(file.end(), {8, 2, 0, 0, 0});  // depth 8, colour type 2 (RGB), deflate, adaptive filtering, no interlace
+    close_chunk(file, at);
+    at = open_chunk(file, "IDAT");
+    z_stream zs;
+    memset(&zs, 0, sizeof(zs));
+    if (deflateInit(&zs, level) != Z_OK) {
+        why = "deflateInit failed";
+        return false;
+    }
+    const size_t head = file.size();
+    file.resize(head + deflateBound(&zs, (uLong)raw.size()));
+    zs.next_in = raw.data();
+    zs.avail_in = (uInt)raw.size();
+    zs.next_out = file.data() + head;
+    zs.avail_out = (uInt)(file.size() - head);
+    const int rc = deflate(&zs, Z_FINISH);
+    const size_t packed = zs.total_out;
+    deflateEnd(&zs);
+    if (rc != Z_STREAM_END) {
+        why = "deflate failed";
+        return false;
+    }
+    file.resize(head + packed);
+    close_chunk(file, at);
+    at = open_chunk(file, "IEND");
+    close_chunk(file, at);
+    return true;
+}
+
+}  // namespace
+
+extern "C" int sd_write_png_batch(const char* const* paths, int n, int H, int W, const uint8_t* rgb, int level,
+                                  int threads, char* err, int errlen) {
+    if (!paths || n < 0 || H <= 0 || W <= 0 || !rgb || level < 0 || level > 9) {
+        if (err && errlen > 0) snprintf(err, (size_t)errlen, "sd_write_png_batch: bad args");
+        return -1;
+    }
+    if (threads > 16) threads = 16;  // a fixed ceiling, not the machine's CPU count
+    if (threads < 1) threads = 1;
+    if (threads > n) threads = n > 0 ? n : 1;
+    const size_t img = (size_t)H * W * 3;
+    std::atomic<int> next{0}, first_bad{n};
+    std::mutex mu;
+    std::string bad_why;
+    auto work = [&]() {
+        std::vector<unsigned char> file, raw;
+        std::string why;
+        for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
+            bool ok = paths[i] != nullptr;
+            if (!ok) why = "null path";
+            if (ok) ok = compose_png(H, W, rgb + i * img, level, file, raw, why);
+            if (ok) ok = write_atomic(paths[i], file, why);
             if (!ok) {
                 std::lock_guard<std::mutex> g(mu);
                 if (i < first_bad.load()) {

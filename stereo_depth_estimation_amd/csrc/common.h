@@ -56,6 +56,29 @@ __device__ __forceinline__ void src_index(int o, int out_size, int in_size, int&
     lam = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
 }
 
+// One output pixel (y, x) of sd_resize_bilinear: the [Hi][Wi] f32 plane `src` sampled at an [Ho][Wo] grid, times mul.
+// k_resize_bilinear (misc.hip) and the export kernels (predict.hip) both take their values from this function, so the
+// upsampled disparity of sd_disp_export equals sd_resize_bilinear bit for bit. The contraction setting is part of that:
+// within a statement (contract(on): the two lerps become FMAs), never across statements, whatever the including file
+// selects for its own code.
+__device__ __forceinline__ float resize_bilinear_px(const float* __restrict__ src, int Hi, int Wi, int Ho, int Wo, int y,
+                                                    int x, float mul) {
+#pragma clang fp contract(on)
+    int y0, y1, x0, x1;
+    float ly, lx;
+    src_index(y, Ho, Hi, y0, y1, ly);
+    src_index(x, Wo, Wi, x0, x1, lx);
+    const float v = (1.f - ly) * ((1.f - lx) * src[y0 * Wi + x0] + lx * src[y0 * Wi + x1]) +
+                    ly * ((1.f - lx) * src[y1 * Wi + x0] + lx * src[y1 * Wi + x1]);
+    return v * mul;
+}
+
+// RGB24 disparity code of the dataset -> f32 (depth_uint8_decoding, reference dataset.py:23-30): the integer is exact in
+// fp32 (< 2^24), one division. sd_stereo_preprocess, the cache kernels and sd_disp_export's ground truth share it.
+__device__ __forceinline__ float decode_rgb24(const uint8_t* px) {
+    return (float)((int)px[0] * 65025 + (int)px[1] * 255 + (int)px[2]) / 1000.f;
+}
+
 // ------------------------------------------------------------------ division by a runtime constant
 // n / d for n < 2^31 as a 64-bit multiply-high (d fixed per launch, m = ceil(2^(32+s) / d))
 struct FastDiv {

@@ -17,9 +17,7 @@ __device__ __forceinline__ float bilerp(float a, float b, float c, float d, floa
     return (a * (1.f - lx) + b * lx) * (1.f - ly) + (c * (1.f - lx) + d * lx) * ly;
 }
 
-__device__ __forceinline__ float decode_rgb24(const uint8_t* px) {
-    return (float)((int)px[0] * 65025 + (int)px[1] * 255 + (int)px[2]) / 1000.f;
-}
+// decode_rgb24: common.h
 
 // The fp32 value of one output pixel from its four taps (top-left, top-right, bottom-left, bottom-right): one colour
 // channel, and the disparity target. k_stereo_preprocess and the cache kernels below all take their values from these

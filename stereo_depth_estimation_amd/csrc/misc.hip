@@ -461,14 +461,7 @@ __global__ void k_resize_bilinear(const float* __restrict__ in, int planes, int 
         const int x = (int)(e % Wo);
         const long long t = e / Wo;
         const int y = (int)(t % Ho), pl = (int)(t / Ho);
-        int y0, y1, x0, x1;
-        float ly, lx;
-        src_index(y, Ho, Hi, y0, y1, ly);
-        src_index(x, Wo, Wi, x0, x1, lx);
-        const float* src = in + (size_t)pl * Hi * Wi;
-        const float v = (1.f - ly) * ((1.f - lx) * src[y0 * Wi + x0] + lx * src[y0 * Wi + x1]) +
-                        ly * ((1.f - lx) * src[y1 * Wi + x0] + lx * src[y1 * Wi + x1]);
-        out[e] = v * mul;
+        out[e] = resize_bilinear_px(in + (size_t)pl * Hi * Wi, Hi, Wi, Ho, Wo, y, x, mul);  // common.h
     }
 }
 

@@ -1,0 +1,195 @@
+// Output stage of the predict-and-evaluate tool (stereo_depth_estimation_amd/predict.py): the heads' f32 maps at the
+// model resolution -> the dataset's RGB24 disparity files at the frames' own resolution, and the rows of the stereo
+// error metrics against the native ground truth, in one pass. Per output pixel (the arithmetic INTEGRATION.md states):
+//
+//   d     = sd_resize_bilinear(disp, [H][W] -> [Hs][Ws], mul), mul = float32(Ws / float(W)): common.h resize_bilinear_px,
+//           the function k_resize_bilinear calls, so d equals that entry point bit for bit; disp_up receives d.
+//   code(v): v not finite -> 0, else c = rint(clip(v * 1000, 0, 16646655)), ties to even (np.round). The product is
+//           formed exactly (fp64 holds a float32 times 1000) and rounded once: rounded to float32 first, 47187 of the
+//           codes between 8192011 and 8388607 would not decode back to the float32 they came from.
+//           R = min(c / 65025, 255), rem = c - 65025 R, G = min(rem / 255, 255), B = rem - 255 G: the inverse of
+//           depth_uint8_decoding. Below c = 16646400 that is R = c / 65025, G = (c / 255) % 255, B = c % 255 and G, B
+//           never reach 255; the 256 codes above it (which R = 256 could not hold in a byte) saturate the digits, up to
+//           (255, 255, 255) = 16646655. Code 0 is the dataset's "no value" (valid = target > 0).
+//   disp_rgb  = code(d)
+//   sigma_rgb = code(expf(0.5f * lv) * mul), lv = the same resize of logvar with mul = 1
+//   metrics : gt = decode_rgb24(px) (common.h, as sd_stereo_preprocess); a pixel counts when gt > 0 and d is finite;
+//           e = |d - gt| in float32. Row of sample b, doubles: [0] n, [1] sum e, [2] sum e^2 (each square exact in fp64),
+//           [3..5] #(e > 1), #(e > 2), #(e > 3), [6] #(e > 3 && e > 0.05f * gt) (D1), [7] 0.
+// The sums have one fixed order: a thread adds its pixels in index order, a block adds its threads by a shuffle tree and
+// its four waves in order into one partial row in `work`, and a second launch adds each sample's partial rows in index
+// order. No atomics; the grid depends on (batch, Hs, Ws) alone, and both store paths walk the same four pixels per
+// thread, so two runs, and the two paths, give the same 64 bits.
+#include <limits.h>
+
+#include "common.h"
+
+// this file's own arithmetic is written as it is meant: nothing here may fuse (e = |d - gt| must see the rounded d)
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int EX_BLOCKS = 128;  // partial rows per sample at most (grid-stride beyond)
+constexpr int EX_ROW = 8;
+
+__device__ __forceinline__ uint32_t disp_code(float v) {
+    if (!(fabsf(v) < INFINITY)) return 0u;  // NaN, +-inf
+    const double p = fmin(fmax((double)v * 1000.0, 0.0), 16646655.0);
+    return (uint32_t)(int)rint(p);
+}
+// the three bytes of a code, R in the low byte (memory order R, G, B)
+__device__ __forceinline__ uint32_t code_bytes(uint32_t c) {
+    const uint32_t r = min(c / 65025u, 255u), rem = c - r * 65025u;
+    const uint32_t g = min(rem / 255u, 255u), b = rem - g * 255u;
+    return r | g << 8 | b << 16;
+}
+
+__device__ __forceinline__ void store_rgb4(uint8_t* dst, const uint32_t (&v)[4]) {  // 12 bytes, 4-B aligned
+    uint32_t* w = reinterpret_cast<uint32_t*>(dst);
+    w[0] = v[0] | v[1] << 24;               // r0 g0 b0 r1
+    w[1] = v[1] >> 8 | v[2] << 16;          // g1 b1 r2 g2
+    w[2] = v[2] >> 16 | v[3] << 8;          // b2 r3 g3 b3
+}
+__device__ __forceinline__ void store_rgb1(uint8_t* dst, uint32_t v) {
+    dst[0] = (uint8_t)v, dst[1] = (uint8_t)(v >> 8), dst[2] = (uint8_t)(v >> 16);
+}
+
+// Four consecutive pixels of a sample's [Hs][Ws] plane per thread (the last thread of an odd plane fewer). VEC: Ws % 4
+// == 0, so the four share a row, and the outputs are aligned: three word stores per image and one 16-B store of
+// disp_up; otherwise byte and float stores, any width and alignment. blockIdx.y = sample.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_disp_export(const float* __restrict__ disp, const float* __restrict__ logvar,
+                                                     int H, int W, const uint8_t* __restrict__ gt_rgb, int Hs, int Ws,
+                                                     float mul, uint8_t* __restrict__ disp_rgb,
+                                                     uint8_t* __restrict__ sigma_rgb, float* __restrict__ disp_up,
+                                                     double* __restrict__ partial) {
+    const int b = blockIdx.y;
+    const int plane = Hs * Ws, quads = (plane + 3) / 4;
+    const float* dsrc = disp + (size_t)b * H * W;
+    const float* lsrc = logvar ? logvar + (size_t)b * H * W : nullptr;
+    const size_t base = (size_t)b * plane;
+    double se = 0.0, se2 = 0.0;
+    unsigned n = 0, c1 = 0, c2 = 0, c3 = 0, cd = 0;
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < quads; q += gridDim.x * 256) {
+        const int e0 = q * 4;
+        const int cnt = VEC ? 4 : min(4, plane - e0);
+        float d[4];
+        uint32_t dc[4] = {0u, 0u, 0u, 0u}, sc[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            if (p < cnt) {
+                const int e = e0 + p, y = e / Ws, x = e - y * Ws;
+                d[p] = resize_bilinear_px(dsrc, H, W, Hs, Ws, y, x, mul);
+                dc[p] = code_bytes(disp_code(d[p]));
+                if (lsrc != nullptr) {
+                    const float lv = resize_bilinear_px(lsrc, H, W, Hs, Ws, y, x, 1.f);
+                    sc[p] = code_bytes(disp_code(expf(0.5f * lv) * mul));
+                }
+                if (partial != nullptr) {
+                    const float gt = decode_rgb24(gt_rgb + (base + e) * 3);
+                    if (gt > 0.f && fabsf(d[p]) < INFINITY) {
+                        const float err = fabsf(d[p] - gt);
+                        const double e64 = (double)err;
+                        ++n;
+                        se += e64;
+                        se2 += e64 * e64;
+                        c1 += err > 1.f;
+                        c2 += err > 2.f;
+                        c3 += err > 3.f;
+                        cd += err > 3.f && err > 0.05f * gt;
+                    }
+                }
+            }
+        }
+        if (VEC) {
+            if (disp_rgb != nullptr) store_rgb4(disp_rgb + (base + e0) * 3, dc);
+            if (sigma_rgb != nullptr) store_rgb4(sigma_rgb + (base + e0) * 3, sc);
+            if (disp_up != nullptr) *reinterpret_cast<float4*>(disp_up + base + e0) = make_float4(d[0], d[1], d[2], d[3]);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                if (p < cnt) {
+                    if (disp_rgb != nullptr) store_rgb1(disp_rgb + (base + e0 + p) * 3, dc[p]);
+                    if (sigma_rgb != nullptr) store_rgb1(sigma_rgb + (base + e0 + p) * 3, sc[p]);
+                    if (disp_up != nullptr) disp_up[base + e0 + p] = d[p];
+                }
+            }
+        }
+    }
+    if (partial == nullptr) return;  // uniform over the grid
+    // the block's row: each wave by a shuffle tree, then the four waves in order (counts are exact as doubles)
+    double v[7] = {(double)n, se, se2, (double)c1, (double)c2, (double)c3, (double)cd};
+    __shared__ double red[4][EX_ROW];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) v[k] += __shfl_down(v[k], s);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) red[threadIdx.x >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < EX_ROW) {
+        const int k = threadIdx.x;
+        double t = 0.0;
+        if (k < 7) t = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+        partial[((size_t)b * gridDim.x + blockIdx.x) * EX_ROW + k] = t;
+    }
+}
+
+// metrics[b][k] = the sample's partial rows added in index order; one block of 64 threads per sample
+__global__ void k_disp_export_rows(const double* __restrict__ partial, int nblk, double* __restrict__ metrics) {
+    const int b = blockIdx.x, k = threadIdx.x;
+    if (k >= EX_ROW) return;
+    double t = 0.0;
+    for (int j = 0; j < nblk; ++j) t += partial[((size_t)b * nblk + j) * EX_ROW + k];
+    metrics[(size_t)b * EX_ROW + k] = t;
+}
+
+int export_blocks(int Hs, int Ws) {  // blocks (= partial rows) per sample: a function of the output size alone
+    const long long quads = ((long long)Hs * Ws + 3) / 4;
+    const long long g = (quads + 255) / 256;
+    return (int)(g > EX_BLOCKS ? EX_BLOCKS : g);
+}
+
+bool export_sizes_ok(int batch, int Hs, int Ws) {
+    return batch > 0 && batch <= 65535 && Hs > 0 && Ws > 0 && (long long)Hs * Ws <= INT_MAX - 3;
+}
+
+}  // namespace
+
+extern "C" long long sd_disp_export_ws_bytes(int batch, int Hs, int Ws) {
+    if (!export_sizes_ok(batch, Hs, Ws)) return -1;
+    return (long long)batch * export_blocks(Hs, Ws) * EX_ROW * (long long)sizeof(double);
+}
+
+extern "C" int sd_disp_export(const float* disp, const float* logvar, int batch, int H, int W, const uint8_t* gt_rgb,
+                              int Hs, int Ws, uint8_t* disp_rgb, uint8_t* sigma_rgb, float* disp_up, double* metrics,
+                              void* work, sd_stream s) {
+    SD_REQUIRE(disp != nullptr, "sd_disp_export: null disp");
+    SD_REQUIRE(H > 0 && W > 0 && (long long)H * W <= INT_MAX, "sd_disp_export: bad model size %d x %d", H, W);
+    SD_REQUIRE(export_sizes_ok(batch, Hs, Ws), "sd_disp_export: bad batch / output size %d, %d x %d", batch, Hs, Ws);
+    SD_REQUIRE(sigma_rgb == nullptr || logvar != nullptr, "sd_disp_export: sigma_rgb needs logvar");
+    SD_REQUIRE(metrics == nullptr || gt_rgb != nullptr, "sd_disp_export: metrics need gt_rgb");
+    SD_REQUIRE(metrics == nullptr || (work != nullptr && (uintptr_t)work % 8 == 0 && (uintptr_t)metrics % 8 == 0),
+               "sd_disp_export: metrics need an 8-B aligned work buffer of sd_disp_export_ws_bytes");
+    SD_REQUIRE(disp_rgb || sigma_rgb || disp_up || metrics, "sd_disp_export: no output requested");
+    // width_scale = upsampled_width / float(model_width) in double, applied as a float32 scalar (sd_stereo_preprocess)
+    const float mul = (float)((double)Ws / (double)W);
+    const bool vec = Ws % 4 == 0 && (uintptr_t)disp_rgb % 4 == 0 && (uintptr_t)sigma_rgb % 4 == 0 &&
+                     (uintptr_t)disp_up % 16 == 0;
+    const int nblk = export_blocks(Hs, Ws);
+    double* partial = metrics ? static_cast<double*>(work) : nullptr;
+    const float* lv = sigma_rgb ? logvar : nullptr;  // the resize of logvar is for sigma alone
+    const dim3 grid(nblk, batch);
+    if (vec)
+        hipLaunchKernelGGL(k_disp_export<true>, grid, dim3(256), 0, to_stream(s), disp, lv, H, W, gt_rgb, Hs, Ws, mul,
+                           disp_rgb, sigma_rgb, disp_up, partial);
+    else
+        hipLaunchKernelGGL(k_disp_export<false>, grid, dim3(256), 0, to_stream(s), disp, lv, H, W, gt_rgb, Hs, Ws, mul,
+                           disp_rgb, sigma_rgb, disp_up, partial);
+    if (metrics)
+        hipLaunchKernelGGL(k_disp_export_rows, dim3(batch), dim3(64), 0, to_stream(s), partial, nblk, metrics);
+    return sd_check_launch("sd_disp_export");
+}

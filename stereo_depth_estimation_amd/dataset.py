@@ -337,6 +337,27 @@ def read_png_batch(paths, size: tuple[int, int], out: torch.Tensor, threads: int
     return rc == 0
 
 
+def write_png_batch(paths, size: tuple[int, int], rgb: torch.Tensor, level: int = 1, threads: int = 16) -> None:
+    """Native (``sd_write_png_batch``) write of n images, a contiguous CPU uint8 [n,H,W,3] tensor, as 8-bit RGB PNGs
+    (filter type 0, zlib ``level`` 0..9) that ``read_png_batch``, ``png_size`` and PIL read back to the same bytes.
+    Each file appears under its name complete or not at all (temporary file + rename); the parent directories must
+    exist. OSError names the first path that failed; the other files of the batch are still written."""
+    H, W = size
+    n = len(paths)
+    if (tuple(rgb.shape) != (n, H, W, 3) or rgb.dtype != torch.uint8 or not rgb.is_contiguous()
+            or rgb.device.type != "cpu"):
+        raise ValueError(f"write_png_batch: expected a contiguous CPU uint8 tensor of {(n, H, W, 3)}, got {rgb.dtype} "
+                         f"{tuple(rgb.shape)}")
+    if not 0 <= int(level) <= 9:
+        raise ValueError(f"write_png_batch: level must be in [0, 9], got {level}")
+    arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(str(p)) for p in paths])
+    err = ctypes.create_string_buffer(1024)
+    rc = L.load().sd_write_png_batch(ctypes.cast(arr, ctypes.c_void_p), n, H, W, rgb.data_ptr(), int(level), threads,
+                                     err, len(err))
+    if rc != 0:
+        raise OSError(f"PNG file could not be written: {err.value.decode(errors='replace')}")
+
+
 def png_size(path) -> tuple[int, int] | None:
     """(H, W) from a PNG's IHDR, None if it is not a PNG."""
     h, w = ctypes.c_int(0), ctypes.c_int(0)

@@ -1,0 +1,468 @@
+"""Predict and evaluate from stereo pairs on disk (no counterpart in the reference).
+
+    python -m stereo_depth_estimation_amd.predict --checkpoint best.pt \\
+        (--dataset-root DIR | --left-dir DIR --right-dir DIR) [--output-root DIR] \\
+        [--height H --width W] [--precision fp32|bf16|fp8] [--base-channels 32] [--batch-size 32] [--max-samples 0] \\
+        [--write-sigma] [--png-level 1] [--read-threads 16] [--device cuda]
+
+Runs a trained checkpoint (``cli.save_checkpoint``'s format, or the reference's) over frames on disk and
+
+* writes each sample's disparity at the frame's own resolution in the dataset's RGB24 encoding (the inverse of
+  ``depth_uint8_decoding``), so that the loader and the cache builder read the files as the labels of a next round:
+  ``<output-root>/<scene>/<frame>.png`` for a FoundationStereo tree (``sample_cache_relpath`` with ``.png``),
+  ``<output-root>/<stem>.png`` for a pair of directories, and ``....sigma.png`` (the predicted standard deviation
+  ``exp(0.5 logvar)`` in pixels of the frame, same encoding) with ``--write-sigma``;
+* with ground truth (``--dataset-root``), evaluates the way stereo work is judged: the prediction upsampled to the
+  native resolution against the native ground truth, EPE, RMSE, bad-1 / bad-2 / bad-3 px and D1, pixel-weighted over
+  all samples (``predict_meta.json``) and per sample (``metrics.jsonl``).
+
+The arithmetic is ``sd_disp_export``'s (include/stereo_hip.h, INTEGRATION.md "Predict and evaluate from files").
+Samples go through a batch at a time: PNG frames are decoded by the threaded native reader into pinned memory (JPEG and
+other PNG kinds by PIL), a side stream copies them up and runs ``sd_stereo_preprocess``, the model's eval forward with
+both heads at batch n and ``sd_disp_export``, 3 bytes per pixel (6 with sigma) plus the metric rows come back, and the
+native PNG writer writes the files; the decode of batch i+1, the device work of batch i and the writing of batch i-1
+overlap. Every sample is written every time (no skip rule), each file under a temporary name and renamed.
+
+``--precision fp8``: the first batch is the calibration forward (its activations set the static e4m3 scales of all
+later batches), and the scales are per tensor over the batch, as in ``LiveDepthBatch``; there are no per-sample scales.
+``--device cpu`` is rejected (no CPU path).
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import time
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .cache import plan_batches
+from .dataset import (discover_samples, read_png_batch, read_rgb_uint8, sample_cache_relpath, write_png_batch)
+
+IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg")
+ROW = 8  # doubles per sample: n, sum e, sum e^2, #(e>1), #(e>2), #(e>3), #D1, 0
+METRIC_KEYS = ("epe", "rmse", "bad1", "bad2", "bad3", "d1")
+
+
+@dataclass(frozen=True)
+class PredictItem:
+    """One stereo pair to process: the frames (disparity_path None: no ground truth) and the output file relative to
+    the output root. The attribute names are ``StereoSample``'s, so ``cache.plan_batches`` groups these too."""
+    left_rgb_path: Path
+    right_rgb_path: Path
+    disparity_path: Path | None
+    relpath: Path
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Predict disparity files from stereo pairs on disk and evaluate them.")
+    p.add_argument("--checkpoint", type=str, required=True, help="Checkpoint of the training CLI (or the reference's).")
+    p.add_argument("--dataset-root", type=str, default=None, help="FoundationStereo tree: ground truth, so metrics.")
+    p.add_argument("--left-dir", type=str, default=None, help="Directory of left frames (paired by stem, no metrics).")
+    p.add_argument("--right-dir", type=str, default=None, help="Directory of right frames.")
+    p.add_argument("--output-root", type=str, default=None, help="Where the disparity PNGs and the metadata go.")
+    p.add_argument("--height", type=int, default=None, help="Model height (default: the checkpoint's).")
+    p.add_argument("--width", type=int, default=None, help="Model width (default: the checkpoint's).")
+    p.add_argument("--precision", type=str, default="fp32", choices=("fp32", "bf16", "fp8"))
+    p.add_argument("--base-channels", type=int, default=32)
+    p.add_argument("--batch-size", type=int, default=32, help="Samples per device batch.")
+    p.add_argument("--max-samples", type=int, default=0, help="Optional cap on number of samples.")
+    p.add_argument("--write-sigma", action="store_true", help="Also write <name>.sigma.png (needs --output-root).")
+    p.add_argument("--png-level", type=int, default=1, help="zlib level of the PNG writer, 0..9.")
+    p.add_argument("--read-threads", type=int, default=16, help="Host threads of the PNG reader and of the writer.")
+    p.add_argument("--device", type=str, default="cuda")
+    return p
+
+
+def _resolve_device(device) -> torch.device:
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"--device {device}: the predict tool runs only on a HIP device (no CPU path).")
+    return dev
+
+
+def pair_by_stem(left_dir, right_dir) -> list[PredictItem]:
+    """The pairs of two directories: image files (.png, .jpg, .jpeg) of equal stem, sorted by stem; a stem present on
+    one side only is ignored. Output ``<stem>.png``."""
+    def frames(d):
+        d = Path(d).expanduser().resolve()
+        if not d.is_dir():
+            raise FileNotFoundError(f"Frame directory does not exist: {d}")
+        out: dict[str, Path] = {}
+        for f in sorted(d.iterdir()):
+            if f.is_file() and f.suffix.lower() in IMAGE_SUFFIXES:
+                out.setdefault(f.stem, f)
+        return out
+
+    left, right = frames(left_dir), frames(right_dir)
+    return [PredictItem(left[k], right[k], None, Path(f"{k}.png")) for k in sorted(left) if k in right]
+
+
+def dataset_items(dataset_root) -> list[PredictItem]:
+    """``discover_samples`` as items: ground truth present, output at ``sample_cache_relpath`` with ``.png``."""
+    return [PredictItem(s.left_rgb_path, s.right_rgb_path, s.disparity_path, sample_cache_relpath(s).with_suffix(".png"))
+            for s in discover_samples(dataset_root)]
+
+
+def sigma_relpath(relpath: Path) -> Path:
+    return relpath.with_suffix(".sigma.png")
+
+
+def metrics_from_row(row) -> dict:
+    """The figures of one row (or of a sum of rows) in fp64; None for each when no pixel counted."""
+    r = [float(v) for v in row]
+    n = r[0]
+    out = {"valid_pixels": int(n)}
+    if n <= 0:
+        out.update({k: None for k in METRIC_KEYS})
+        return out
+    out.update(epe=r[1] / n, rmse=math.sqrt(r[2] / n), bad1=r[3] / n, bad2=r[4] / n, bad3=r[5] / n, d1=r[6] / n)
+    return out
+
+
+def aggregate_rows(rows) -> dict:
+    """Pixel-weighted figures over samples: the rows [N][8] summed column-wise in fp64, then ``metrics_from_row``."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, ROW)
+    return metrics_from_row(rows.sum(axis=0))
+
+
+class Predictor:
+    """The device work of one batch: ``sd_stereo_preprocess``, the model's eval forward with both heads,
+    ``sd_disp_export``. ``model``: a StereoUNet (in_channels 6) on a HIP device, put into eval mode here; ``model_size``
+    = (width, height) at which it runs, as ``LiveDepthBatch``'s. With precision "fp8" the first ``run`` is the
+    calibration forward and the scales are per tensor over the batch."""
+
+    def __init__(self, model, model_size):
+        L.load()
+        self.model = model.eval()
+        self.W, self.H = int(model_size[0]), int(model_size[1])
+        if self.H <= 0 or self.W <= 0 or self.H % 16 or self.W % 16:
+            raise ValueError(f"model_size must be positive multiples of 16 (width, height), got {tuple(model_size)}")
+        self.device = next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError(f"Predictor runs only on a HIP device (no CPU path); the model is on {self.device}")
+        self._calibrated = False
+        self._buf: dict = {}
+
+    def _buffers(self, n: int, Hs: int, Ws: int, sigma: bool) -> dict:
+        """Device buffers for batches of up to n samples of one source size (grown, never shrunk)."""
+        key = (Hs, Ws)
+        b = self._buf.get(key)
+        if b is None or b["n"] < n or (sigma and b["sigma_rgb"] is None):
+            dev, H, W = self.device, self.H, self.W
+            nb = max(n, b["n"]) if b is not None else n
+            with torch.inference_mode(False):
+                b = {"n": nb,
+                     "input": torch.empty(nb, 6, H, W, device=dev),
+                     "target": torch.empty(nb, 1, H, W, device=dev),
+                     "valid": torch.empty(nb, 1, H, W, device=dev, dtype=torch.bool),
+                     "disp_rgb": torch.empty(nb, Hs, Ws, 3, device=dev, dtype=torch.uint8),
+                     "sigma_rgb": torch.empty(nb, Hs, Ws, 3, device=dev, dtype=torch.uint8) if sigma else None,
+                     "rows": torch.empty(nb, ROW, device=dev, dtype=torch.float64),
+                     "work": torch.empty(max(L.call("sd_disp_export_ws_bytes", nb, Hs, Ws), 8) // 8, device=dev,
+                                         dtype=torch.float64)}
+            self._buf[key] = b
+        return b
+
+    def run(self, left_u8: torch.Tensor, right_u8: torch.Tensor, gt_rgb: torch.Tensor | None = None,
+            sigma: bool = False, images: bool = True) -> dict:
+        """left_u8, right_u8 (and gt_rgb, the RGB24 ground truth): contiguous uint8 [n,Hs,Ws,3] on the model's device.
+        Queues the batch on the current stream and returns device tensors without synchronising: ``disp_rgb`` and
+        ``sigma_rgb`` uint8 [n,Hs,Ws,3] (None unless asked for), ``rows`` float64 [n,8] (None without gt_rgb). They are
+        views of buffers the next ``run`` at this source size overwrites."""
+        n, Hs, Ws = (int(v) for v in left_u8.shape[:3])
+        for name, t in (("left_u8", left_u8), ("right_u8", right_u8), ("gt_rgb", gt_rgb)):
+            if t is None:
+                continue
+            if (tuple(t.shape) != (n, Hs, Ws, 3) or t.dtype != torch.uint8 or not t.is_contiguous()
+                    or t.device != self.device):
+                raise ValueError(f"Predictor.run: {name} must be a contiguous uint8 tensor of {(n, Hs, Ws, 3)} on "
+                                 f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        if not (images or gt_rgb is not None):
+            raise ValueError("Predictor.run: neither images nor metrics requested")
+        sigma = bool(sigma and images)
+        b = self._buffers(n, Hs, Ws, sigma)
+        H, W = self.H, self.W
+        with torch.cuda.device(self.device):
+            s = L.stream_handle(self.device)
+            # without ground truth the left frame stands in for the disparity image: target / valid are not used
+            L.call("sd_stereo_preprocess", left_u8.data_ptr(), right_u8.data_ptr(),
+                   (gt_rgb if gt_rgb is not None else left_u8).data_ptr(), n, Hs, Ws, H, W, b["input"].data_ptr(),
+                   b["target"].data_ptr(), b["valid"].data_ptr(), s)
+            x = b["input"][:n]
+            with torch.inference_mode():
+                if not self._calibrated and getattr(self.model, "precision", None) == "fp8":
+                    disp, logvar = self.model.calibrate(x)
+                else:
+                    disp, logvar = self.model(x, return_uncertainty=True)
+            self._calibrated = True
+            L.call("sd_disp_export", disp.data_ptr(), logvar.data_ptr() if sigma else None, n, H, W,
+                   gt_rgb.data_ptr() if gt_rgb is not None else None, Hs, Ws,
+                   b["disp_rgb"].data_ptr() if images else None, b["sigma_rgb"].data_ptr() if sigma else None, None,
+                   b["rows"].data_ptr() if gt_rgb is not None else None, b["work"].data_ptr(), s)
+        return {"disp_rgb": b["disp_rgb"][:n] if images else None, "sigma_rgb": b["sigma_rgb"][:n] if sigma else None,
+                "rows": b["rows"][:n] if gt_rgb is not None else None}
+
+
+class PredictPipeline:
+    """The three stages over two sets of host buffers (slots), shaped like ``cache.CachePipeline``. ``decode`` fills a
+    slot's pinned source frames, ``device`` queues the copies up, ``Predictor.run`` and the copies back on a side
+    stream and returns their event, ``write`` waits for that event, writes the files and returns the rows. A slot's
+    source frames may be refilled once its event has completed, its outputs once its write has returned. Host and
+    device buffers are made once per source size (and slot) and reused by every later batch of that size."""
+
+    def __init__(self, predictor: Predictor, batch_size: int, has_gt: bool, images: bool, sigma: bool,
+                 png_level: int = 1, read_threads: int = 16):
+        self.p, self.bmax, self.has_gt, self.images, self.sigma = predictor, batch_size, has_gt, images, sigma and images
+        self.level, self.threads = png_level, read_threads
+        self.device = predictor.device
+        self.stream = torch.cuda.Stream(self.device)
+        self._src = [{}, {}]  # per slot: source size -> pinned uint8 [bmax,Hs,Ws,3] per frame kind
+        self._out = [{}, {}]  # per slot: source size -> (disp_rgb, sigma_rgb, rows) pinned
+        self._dev: dict = {}  # source size -> device uint8 [bmax,Hs,Ws,3] per frame kind
+
+    def _kinds(self):
+        return ("left_rgb_path", "right_rgb_path") + (("disparity_path",) if self.has_gt else ())
+
+    def _pinned_src(self, slot: int, hw):
+        if hw not in self._src[slot]:
+            self._src[slot][hw] = tuple(torch.empty(self.bmax, *hw, 3, dtype=torch.uint8).pin_memory()
+                                        for _ in self._kinds())
+        return self._src[slot][hw]
+
+    def _pinned_out(self, slot: int, hw):
+        if hw not in self._out[slot]:
+            img = lambda: torch.empty(self.bmax, *hw, 3, dtype=torch.uint8).pin_memory()  # noqa: E731
+            self._out[slot][hw] = (img() if self.images else None, img() if self.sigma else None,
+                                   torch.zeros(self.bmax, ROW, dtype=torch.float64).pin_memory())
+        return self._out[slot][hw]
+
+    def decode(self, slot: int, hw, items) -> list[tuple]:
+        """Source frames of one batch as parts (left, right[, ground truth]), each uint8 [n,Hs,Ws,3] pinned and of one
+        source size, in the batch's order."""
+        n, kinds = len(items), self._kinds()
+        if hw is not None:
+            views = tuple(t[:n] for t in self._pinned_src(slot, hw))
+            if all(read_png_batch([getattr(s, a) for s in items], hw, v, self.threads) for a, v in zip(kinds, views)):
+                return [views]
+        # PIL for these frames (JPEG, other PNG kinds, or sizes that differ from the left frame's)
+        parts, run, run_shape = [], [], None
+        for s in items:
+            f = [read_rgb_uint8(getattr(s, a)) for a in kinds]
+            if any(a.shape != f[0].shape for a in f):
+                raise ValueError(f"left/right/disparity sizes differ for sample {s.disparity_path or s.left_rgb_path}")
+            if run and f[0].shape != run_shape:
+                parts.append(run)
+                run = []
+            run_shape = f[0].shape
+            run.append(f)
+        parts.append(run)
+        return [tuple(torch.from_numpy(np.stack([f[a] for f in run])).pin_memory() for a in range(len(kinds)))
+                for run in parts]
+
+    def device_work(self, slot: int, parts):
+        """Queues one batch on the side stream. Returns (event, [(n, (Hs, Ws), pinned disp_rgb, sigma_rgb, rows)])."""
+        dev, outs = self.device, []
+        with torch.cuda.stream(self.stream):
+            off: dict = {}
+            for part in parts:
+                n, Hs, Ws = (int(v) for v in part[0].shape[:3])
+                hw = (Hs, Ws)
+                if hw not in self._dev or self._dev[hw][0].shape[0] < n:
+                    self._dev[hw] = tuple(torch.empty(max(n, self.bmax), Hs, Ws, 3, dtype=torch.uint8, device=dev)
+                                          for _ in part)
+                up = tuple(d[:n] for d in self._dev[hw])
+                for d, h in zip(up, part):
+                    d.copy_(h, non_blocking=True)
+                res = self.p.run(up[0], up[1], up[2] if self.has_gt else None, sigma=self.sigma, images=self.images)
+                o = off.get(hw, 0)  # parts of one size within a batch share the slot's buffers
+                off[hw] = o + n
+                h_disp, h_sigma, h_rows = self._pinned_out(slot, hw)
+                if o + n > self.bmax:
+                    raise RuntimeError("a batch holds more samples of one size than the batch size")
+                if self.images:
+                    h_disp[o:o + n].copy_(res["disp_rgb"], non_blocking=True)
+                if self.sigma:
+                    h_sigma[o:o + n].copy_(res["sigma_rgb"], non_blocking=True)
+                if self.has_gt:
+                    h_rows[o:o + n].copy_(res["rows"], non_blocking=True)
+                outs.append((n, hw, h_disp[o:o + n] if self.images else None,
+                             h_sigma[o:o + n] if self.sigma else None, h_rows[o:o + n]))
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        return ev, outs
+
+    def write(self, paths, sigma_paths, ev: torch.cuda.Event, outs) -> np.ndarray:
+        """Waits for the batch, writes its files (paths: one per sample in batch order, or None) and returns its rows."""
+        ev.synchronize()
+        k, rows = 0, []
+        for n, hw, h_disp, h_sigma, h_rows in outs:
+            if paths is not None and h_disp is not None:
+                write_png_batch(paths[k:k + n], hw, h_disp, self.level, self.threads)
+            if sigma_paths is not None and h_sigma is not None:
+                write_png_batch(sigma_paths[k:k + n], hw, h_sigma, self.level, self.threads)
+            rows.append(h_rows.numpy().copy())
+            k += n
+        return np.concatenate(rows) if rows else np.zeros((0, ROW))
+
+
+def load_model(checkpoint, precision: str = "fp32", base_channels: int = 32, device="cuda"):
+    """The checkpoint's model in eval mode on the device and the checkpoint dict (``cli.load_checkpoint``)."""
+    from .cli import load_checkpoint
+    from .model import StereoUNet
+
+    model = StereoUNet(in_channels=6, out_channels=1, base_channels=base_channels, precision=precision)
+    ck = load_checkpoint(checkpoint, model, None, device)
+    return model.eval(), ck
+
+
+def _run(items: list[PredictItem], mode: str, source: str, described: dict, checkpoint, model, output_root, height,
+         width, precision, base_channels, batch_size, max_samples, write_sigma, png_level, read_threads, device) -> dict:
+    dev = _resolve_device(device)
+    if batch_size < 1:
+        raise ValueError(f"--batch-size must be >= 1, got: {batch_size}")
+    if not 0 <= png_level <= 9:
+        raise ValueError(f"--png-level must be in [0, 9], got: {png_level}")
+    has_gt = mode == "dataset"
+    if output_root is None and not has_gt:
+        raise ValueError("Nothing to do: no ground truth to evaluate against and no --output-root to write to.")
+    if write_sigma and output_root is None:
+        raise ValueError("--write-sigma needs --output-root.")
+    if max_samples > 0:
+        items = items[:max_samples]
+    if not items:
+        raise ValueError(f"No samples discovered under: {source}")
+
+    started_at = time.time()
+    if model is None:
+        model, ck = load_model(checkpoint, precision, base_channels, dev)
+        ck_args = ck.get("args") or {}
+        height = height if height is not None else ck_args.get("height")
+        width = width if width is not None else ck_args.get("width")
+    else:
+        if next(model.parameters()).device.type != "cuda":  # (.to() on a model already there would re-flatten it)
+            model = model.to(dev)
+        precision, base_channels = model.precision, model.base_channels
+    if height is None or width is None:
+        raise ValueError("--height / --width: the checkpoint carries no args to take them from; pass both.")
+    out_root = None
+    if output_root is not None:
+        out_root = Path(output_root).expanduser().resolve()
+        out_root.mkdir(parents=True, exist_ok=True)
+        for d in sorted({(out_root / it.relpath).parent for it in items}):
+            d.mkdir(parents=True, exist_ok=True)
+
+    batches = plan_batches(items, batch_size)
+    predictor = Predictor(model, (width, height))
+    pipe = PredictPipeline(predictor, batch_size, has_gt, out_root is not None, write_sigma, png_level, read_threads)
+    events, writes, held = [None, None], [None, None], [None, None]
+    done: list = []  # (batch's items, future of its rows) in order
+    try:
+        with ThreadPoolExecutor(1) as reader, ThreadPoolExecutor(1) as writer:
+            fut = reader.submit(pipe.decode, 0, *batches[0])
+            for i, (_, its) in enumerate(batches):
+                k = i & 1
+                parts = fut.result()
+                if i + 1 < len(batches):
+                    if events[k ^ 1] is not None:
+                        events[k ^ 1].synchronize()  # the other slot's source frames are on the device
+                    fut = reader.submit(pipe.decode, k ^ 1, *batches[i + 1])
+                if writes[k] is not None:
+                    writes[k].result()  # this slot's outputs are on disk
+                events[k], outs = pipe.device_work(k, parts)
+                held[k] = parts  # pinned frames stay alive until their copies are done (the slot's next turn)
+                paths = [out_root / it.relpath for it in its] if out_root is not None else None
+                spaths = [out_root / sigma_relpath(it.relpath) for it in its] if (out_root and write_sigma) else None
+                writes[k] = writer.submit(pipe.write, paths, spaths, events[k], outs)
+                done.append((its, writes[k]))
+            rows = [(its, w.result()) for its, w in done]
+    finally:
+        pipe.stream.synchronize()
+
+    elapsed = time.time() - started_at
+    meta = {
+        "format_version": 1,
+        "mode": mode,
+        **described,
+        "checkpoint": str(checkpoint) if checkpoint is not None else None,
+        "output_root": str(out_root) if out_root is not None else None,
+        "height": int(height),
+        "width": int(width),
+        "precision": precision,
+        "base_channels": int(base_channels),
+        "batch_size": int(batch_size),
+        "max_samples": int(max_samples),
+        "write_sigma": bool(write_sigma),
+        "png_level": int(png_level),
+        "read_threads": int(read_threads),
+        "num_samples": len(items),
+        "num_batches": len(batches),
+        "num_written": len(items) * (1 + bool(write_sigma)) if out_root is not None else 0,
+        "elapsed_seconds": elapsed,
+        "created_at_unix": time.time(),
+    }
+    if has_gt:
+        all_rows = np.concatenate([r for _, r in rows])
+        meta.update(aggregate_rows(all_rows))
+        if out_root is not None:
+            with open(out_root / "metrics.jsonl", "w", encoding="utf-8") as f:
+                for (its, r) in rows:
+                    for it, row in zip(its, r):
+                        f.write(json.dumps({"sample": it.relpath.as_posix(), **metrics_from_row(row)}) + "\n")
+    if out_root is not None:
+        (out_root / "predict_meta.json").write_text(json.dumps(meta, indent=2), encoding="utf-8")
+    print(json.dumps(meta))
+    return meta
+
+
+def predict_dataset(checkpoint, dataset_root, output_root=None, *, model=None, height=None, width=None,
+                    precision: str = "fp32", base_channels: int = 32, batch_size: int = 32, max_samples: int = 0,
+                    write_sigma: bool = False, png_level: int = 1, read_threads: int = 16, device="cuda") -> dict:
+    """A FoundationStereo tree: disparity files under output_root (if given) and the metrics against the tree's ground
+    truth. ``model``: a StereoUNet to use instead of loading ``checkpoint`` (height and width are then required).
+    Returns the dict that is also written to ``predict_meta.json`` and printed as one JSON line."""
+    _resolve_device(device)
+    root = Path(dataset_root).expanduser().resolve()
+    items = dataset_items(root)
+    return _run(items, "dataset", str(root), {"dataset_root": str(root)}, checkpoint, model, output_root,
+                height, width, precision, base_channels, batch_size, max_samples, write_sigma, png_level, read_threads,
+                device)
+
+
+def predict_pairs(checkpoint, left_dir, right_dir, output_root, *, model=None, height=None, width=None,
+                  precision: str = "fp32", base_channels: int = 32, batch_size: int = 32, max_samples: int = 0,
+                  write_sigma: bool = False, png_level: int = 1, read_threads: int = 16, device="cuda") -> dict:
+    """Two directories of frames paired by stem: ``<output_root>/<stem>.png``, no metrics."""
+    _resolve_device(device)
+    if output_root is None:
+        raise ValueError("Nothing to do: no ground truth to evaluate against and no --output-root to write to.")
+    left, right = Path(left_dir).expanduser().resolve(), Path(right_dir).expanduser().resolve()
+    items = pair_by_stem(left, right)
+    return _run(items, "pairs", f"{left} + {right}", {"left_dir": str(left), "right_dir": str(right)}, checkpoint,
+                model, output_root, height, width, precision, base_channels, batch_size, max_samples,
+                write_sigma, png_level, read_threads, device)
+
+
+def main(argv=None) -> dict:
+    parser = build_parser()
+    a = parser.parse_args(argv)
+    _resolve_device(a.device)
+    dirs = a.left_dir is not None or a.right_dir is not None
+    if (a.dataset_root is not None) == dirs or (dirs and (a.left_dir is None or a.right_dir is None)):
+        parser.error("give either --dataset-root or both --left-dir and --right-dir")
+    common = dict(height=a.height, width=a.width, precision=a.precision, base_channels=a.base_channels,
+                  batch_size=a.batch_size, max_samples=a.max_samples, write_sigma=a.write_sigma, png_level=a.png_level,
+                  read_threads=a.read_threads, device=a.device)
+    if a.dataset_root is not None:
+        return predict_dataset(a.checkpoint, a.dataset_root, a.output_root, **common)
+    return predict_pairs(a.checkpoint, a.left_dir, a.right_dir, a.output_root, **common)
+
+
+if __name__ == "__main__":
+    main()
