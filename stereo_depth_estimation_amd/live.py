@@ -204,6 +204,64 @@ def _per_stream(value, streams: int, name: str) -> list:
     return [value] * streams
 
 
+def stream_rectification(rectification, streams: int):
+    """None, one rectification object shared by all streams, or a list of one per stream (all of one image_size) ->
+    (one object per stream or None, shared_maps, image_size or None)."""
+    shared = not isinstance(rectification, (list, tuple))
+    if rectification is None:
+        return None, shared, None
+    rects = _per_stream(rectification, streams, "rectification")
+    if any(r is None for r in rects):
+        raise ValueError("rectification: a sequence must hold one object per stream (no None entries)")
+    sizes = {tuple(r.image_size) for r in rects}
+    if len(sizes) > 1:
+        raise ValueError(f"rectification: all streams must have one image_size, got {sorted(sizes)}")
+    return rects, shared, sizes.pop()
+
+
+def upload_maps(rects, side: str, H: int, W: int, device) -> tuple[torch.Tensor, torch.Tensor]:
+    """Side "l" or "r" of the objects' fixed-point maps, checked and stacked on the device: map1 int16
+    [len(rects), H, W, 2] and map2 as int16 [len(rects), H, W] (the uint16's bits)."""
+    m1s, m2s = [], []
+    for r in rects:
+        m1 = np.ascontiguousarray(getattr(r, f"map_{side}_1"))
+        m2 = np.ascontiguousarray(getattr(r, f"map_{side}_2"))
+        if m1.shape != (H, W, 2) or m1.dtype != np.int16 or m2.shape != (H, W) or m2.dtype != np.uint16:
+            raise ValueError("rectification maps: map1 int16 [H, W, 2] and map2 uint16 [H, W] "
+                             "(cv2.initUndistortRectifyMap(..., cv2.CV_16SC2) or live.rectify_maps)")
+        m1s.append(m1)
+        m2s.append(m2.view(np.int16))
+    return torch.as_tensor(np.stack(m1s)).to(device), torch.as_tensor(np.stack(m2s)).to(device)
+
+
+def colormap_table(colormap) -> np.ndarray:
+    """A name of COLORMAP_NAMES or a [256, 3] uint8 BGR table -> the table, contiguous."""
+    lut = colormap_lut(colormap) if isinstance(colormap, str) else np.asarray(colormap)
+    if lut.shape != (256, 3) or lut.dtype != np.uint8:
+        raise ValueError("colormap: a name or a [256, 3] uint8 BGR table")
+    return np.ascontiguousarray(lut)
+
+
+class PinnedRing:
+    """Three pinned uint8 staging buffers of one shape for numpy frames, filled in turn: a slot is written again only
+    after its upload of three steps ago has completed, so a step never waits unless frames queue up."""
+
+    def __init__(self, shape):
+        self.pin = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(3)]
+        self._events = [torch.cuda.Event() for _ in range(3)]
+        self._slot = -1
+
+    def take(self) -> tuple[int, np.ndarray]:
+        """The next slot and the numpy view of pin[slot], once the slot's last upload is complete."""
+        self._slot = (self._slot + 1) % 3
+        self._events[self._slot].synchronize()  # returns at once for a slot that has not been uploaded yet
+        return self._slot, self.pin[self._slot].numpy()
+
+    def record(self, device) -> None:
+        """After the caller's non_blocking copies out of the slot taken last."""
+        self._events[self._slot].record(torch.cuda.current_stream(device))
+
+
 class LiveDepthBatch:
     """The frame path for `streams` camera pairs of one capture size and one model: one front-end launch, one batch-N
     forward and one launch sequence of the display stage per step, whatever N is.
@@ -239,20 +297,12 @@ class LiveDepthBatch:
         self.W, self.H = int(model_size[0]), int(model_size[1])
         if self.H % 16 or self.W % 16 or self.H <= 0 or self.W <= 0:
             raise ValueError("model_size must be positive multiples of 16 (four 2x2 pools)")
-        self.shared_maps = not isinstance(rectification, (list, tuple))
-        rects = _per_stream(rectification, n, "rectification")
-        if rectification is not None and any(r is None for r in rects):
-            raise ValueError("rectification: a sequence must hold one object per stream (no None entries)")
-        sizes = {tuple(r.image_size) for r in rects if r is not None}
-        if len(sizes) > 1:
-            raise ValueError(f"rectification: all streams must have one image_size, got {sorted(sizes)}")
-        self.rectification = None if rectification is None else rects
-        self.image_size = sizes.pop() if sizes else None
+        self.rectification, self.shared_maps, self.image_size = stream_rectification(rectification, n)
         focal = _per_stream(focal_length_px, n, "focal_length_px")
         base = _per_stream(baseline_m, n, "baseline_m")
         width = _per_stream(calibration_width_px, n, "calibration_width_px")
         self.focal_length_px_model, self.baseline_m = [], []
-        for i, r in enumerate(rects):
+        for i, r in enumerate(self.rectification or [None] * n):
             f, b, w = (r.focal_length_px, r.baseline_m, r.image_size[0]) if r is not None else (focal[i], base[i], width[i])
             fm = f * (self.W / float(w)) if f is not None and w is not None and w > 0 else None
             self.focal_length_px_model.append(fm)
@@ -265,15 +315,11 @@ class LiveDepthBatch:
         self.uncertainty = bool(uncertainty)
         self.ema_alpha = float(ema_alpha)
         self.center_window = int(center_window)
-        lut = colormap_lut(colormap) if isinstance(colormap, str) else np.asarray(colormap)
-        if lut.shape != (256, 3) or lut.dtype != np.uint8:
-            raise ValueError("colormap: a name or a [256, 3] uint8 BGR table")
-        self._lut_host = (np.ascontiguousarray(lut), colormap_lut(CONFIDENCE_COLORMAP))
+        self._lut_host = (colormap_table(colormap), colormap_lut(CONFIDENCE_COLORMAP))
         self._first = [True] * n  # the stream's next fresh frame is copied into the EMA state
         self._seen = [False] * n  # the stream has had a fresh frame since the buffers were made
         self._buf = None
         self._key = None
-        self._stage_i = 0
 
     def reset(self, stream=None) -> None:
         """Forget the EMA state of one stream, or of all: its next fresh frame's prediction is taken as is."""
@@ -304,28 +350,16 @@ class LiveDepthBatch:
                 "sel": torch.zeros((n, 8), dtype=f32, device=device),
                 "sel_ws": torch.zeros(L.call("sd_live_select_n_ws_bytes", n) // 4, dtype=torch.int32, device=device),
                 "lut_a": torch.as_tensor(self._lut_host[0]).to(device), "lut_b": torch.as_tensor(self._lut_host[1]).to(device),
-                # numpy frames: a ring of pinned staging buffers [side][stream] (a slot is reused three steps later) and
-                # ONE device copy, in which a held stream's slices keep its previous frame
-                "pin": [torch.empty((2, n, Hc, Wc, 3), dtype=u8, pin_memory=True) for _ in range(3)],
-                "pin_ev": [None, None, None],
+                # numpy frames: pinned staging buffers [side][stream] and ONE device copy, in which a held stream's
+                # slices keep its previous frame
+                "ring": PinnedRing((2, n, Hc, Wc, 3)),
                 "frames": dev((2, n, Hc, Wc, 3), u8),
                 "center_host": torch.full((n, 3), float("nan"), dtype=f32, pin_memory=True),
             }
             if self.rectification is not None:
                 rects = self.rectification[:1] if self.shared_maps else self.rectification
                 for side in ("l", "r"):
-                    m1s, m2s = [], []
-                    for r in rects:
-                        m1 = np.ascontiguousarray(getattr(r, f"map_{side}_1"))
-                        m2 = np.ascontiguousarray(getattr(r, f"map_{side}_2"))
-                        if m1.shape != (Hc, Wc, 2) or m1.dtype != np.int16 or m2.shape != (Hc, Wc) \
-                                or m2.dtype != np.uint16:
-                            raise ValueError("rectification maps: map1 int16 [Hc, Wc, 2] and map2 uint16 [Hc, Wc] "
-                                             "(cv2.initUndistortRectifyMap(..., cv2.CV_16SC2) or rectify_maps)")
-                        m1s.append(m1)
-                        m2s.append(m2.view(np.int16))
-                    b[f"m1{side}"] = torch.as_tensor(np.stack(m1s)).to(device)
-                    b[f"m2{side}"] = torch.as_tensor(np.stack(m2s)).to(device)
+                    b[f"m1{side}"], b[f"m2{side}"] = upload_maps(rects, side, Hc, Wc, device)
         self._buf, self._key = b, (device, Hc, Wc)
         self._first = [True] * n
         self._seen = [False] * n
@@ -369,13 +403,7 @@ class LiveDepthBatch:
             if any(f.dtype != np.uint8 for f in ([side] if isinstance(side, np.ndarray) else side)):
                 raise ValueError("frames must be uint8")
         b = self._buf
-        i = self._stage_i
-        self._stage_i = (i + 1) % 3
-        if b["pin_ev"][i] is not None:
-            b["pin_ev"][i].synchronize()  # the upload of three steps ago: long complete unless frames queue up
-        else:
-            b["pin_ev"][i] = torch.cuda.Event()
-        pin = b["pin"][i].numpy()
+        i, pin = b["ring"].take()
         runs, k = [], 0  # [k0, k1) runs of fresh streams
         while k < n:
             if not fresh[k]:
@@ -388,12 +416,12 @@ class LiveDepthBatch:
                 k += 1
             runs.append((k0, k))
         if runs == [(0, n)]:
-            b["frames"].copy_(b["pin"][i], non_blocking=True)
+            b["frames"].copy_(b["ring"].pin[i], non_blocking=True)
         else:
             for k0, k1 in runs:
                 for side in (0, 1):
-                    b["frames"][side, k0:k1].copy_(b["pin"][i][side, k0:k1], non_blocking=True)
-        b["pin_ev"][i].record(torch.cuda.current_stream(device))
+                    b["frames"][side, k0:k1].copy_(b["ring"].pin[i][side, k0:k1], non_blocking=True)
+        b["ring"].record(device)
         return b["frames"][0], b["frames"][1]
 
     # ------------------------------------------------------------------ one step of all streams

@@ -238,7 +238,8 @@ def test_post_stage_is_bit_equal(calib_Q, which):
 
 # ---------------------------------------------------------------------- the whole loop body
 def _stagewise(classic, fl, fr, maps):
-    """ClassicDepth.step's outputs from separate entry-point calls on fresh buffers."""
+    """ClassicDepth.step's outputs from separate single-stream entry-point calls on fresh buffers (the matcher's
+    workspace filled with 0xFF): no Python of the package's frame path is shared with the step under test."""
     H, W = fl.shape[:2]
     s = _s()
     rect = []
@@ -255,7 +256,12 @@ def _stagewise(classic, fl, fr, maps):
         g = torch.empty((H, W), dtype=torch.uint8, device=DEV)
         L.call("sd_sgm_gray", t.data_ptr(), H, W, g.data_ptr(), s)
         gray.append(g)
-    q = classic.matcher.__class__(**MATCHER_KW).compute(gray[0], gray[1])
+    p = R.Params(**MATCHER_KW)
+    ws = torch.full((L.call("sd_sgm_ws_bytes", H, W, p.D),), 0xFF, dtype=torch.uint8, device=DEV)
+    q = torch.empty((H, W), dtype=torch.int16, device=DEV)
+    L.call("sd_sgm_compute_mode", gray[0].data_ptr(), gray[1].data_ptr(), H, W, p.minD, p.D, p.bs, p.P1, p.P2,
+           p.max_diff, p.uniq, p.speckle_window, p.speckle_range, p.cap, L.SD_SGM_MODE_3WAY, ws.data_ptr(),
+           q.data_ptr(), s)
     disp, z, code, c = _post(_np(q), classic.Q, classic.center_window)
     vis = live.colormap_lut("turbo")[code]
     return rect, q, disp, z, vis, c
@@ -278,6 +284,9 @@ def test_classic_depth_step(calib_Q, with_maps):
 
     def check(res, a, b):
         want_rect, q, disp, z, vis, c = _stagewise(classic, a, b, maps)
+        assert all(tuple(getattr(res, k).shape) == (H, W) for k in ("disparity_q4", "disparity", "depth_m"))
+        assert all(tuple(getattr(res, k).shape) == (H, W, 3) for k in ("rect_left", "rect_right", "disp_vis"))
+        assert type(res.readout()) is float
         assert torch.equal(res.rect_left, want_rect[0]) and torch.equal(res.rect_right, want_rect[1])
         assert res.disparity_q4.dtype == torch.int16 and torch.equal(res.disparity_q4, q)
         _assert_bit_equal(_np(res.disparity), disp)
@@ -292,7 +301,10 @@ def test_classic_depth_step(calib_Q, with_maps):
         assert (q[:, 16:] != -16).mean() > 0.5
     # device frames; a second step at the size allocates nothing
     dl, dr = _dev(fl), _dev(fr)
-    check(classic.step(dl, dr), fl, fr)
+    res = classic.step(dl, dr)
+    if not with_maps:  # frames taken as rectified are handed back as they came: the caller's own tensors
+        assert res.rect_left is dl and res.rect_right is dr
+    check(res, fl, fr)
     torch.cuda.synchronize()
     before = torch.cuda.memory_allocated()
     res = classic.step(dl, dr)

@@ -144,6 +144,31 @@ def test_every_stream_equals_the_single_stream_matcher(case):
         assert all((r["q"]["3way"] == p.invalid).all() for r in refs)
 
 
+def test_one_matcher_serves_one_pair_and_batches_from_one_workspace():
+    """compute, compute_batch on 3 pairs and compute again on one StereoSGM object: after the first round (which grows
+    the workspace to the batch's size) nothing is allocated, and every result is a fresh matcher's, bit for bit."""
+    case = CASES[0]
+    H, W, D, minD, bs = case
+    kw = dict(min_disparity=minD, num_disparities=D, block_size=bs, speckle_window_size=_params(case).speckle_window)
+    refs = [_ref(case, i) for i in range(N)]
+    gl = _dev(np.stack([r["gray_l"] for r in refs]))
+    gr = _dev(np.stack([r["gray_r"] for r in refs]))
+    m = sgm.StereoSGM(**kw)
+    allocated = []
+    for _ in range(3):
+        got = [m.compute(gl[0], gr[0]), m.compute_batch(gl, gr), m.compute(gl[2], gr[2])]
+        torch.cuda.synchronize()
+        allocated.append(torch.cuda.memory_allocated())
+        assert m.workspace(gl.device, H, W).numel() == L.call("sd_sgm_ws_bytes_n", N, H, W, D)
+        assert torch.equal(got[0], sgm.StereoSGM(**kw).compute(gl[0], gr[0]))
+        assert torch.equal(got[1], sgm.StereoSGM(**kw).compute_batch(gl, gr))
+        assert torch.equal(got[2], sgm.StereoSGM(**kw).compute(gl[2], gr[2]))
+        assert tuple(got[0].shape) == (H, W) and tuple(got[1].shape) == (N, H, W)
+        for i in range(N):
+            assert np.array_equal(_np(got[1][i]), refs[i]["q"]["3way"]), i
+    assert allocated[1] == allocated[0] and allocated[2] == allocated[0]
+
+
 # ---------------------------------------------------------------------- 2: isolation
 @pytest.mark.parametrize("mode", ["3way", "hh"])
 def test_a_stream_depends_on_its_own_pair_only(mode):
@@ -245,6 +270,9 @@ MATCHER_KW = dict(num_disparities=16, block_size=5, speckle_window_size=10)
 @pytest.mark.parametrize("with_maps", [False, True], ids=["no_maps", "per_stream_maps"])
 @pytest.mark.parametrize("mode", ["3way", "hh"])
 def test_classic_depth_batch_step(calib_Q, mode, with_maps):
+    """A stream's bytes do not depend on n: every stream of a 3-rig step equals a ClassicDepth (the same
+    implementation with n = 1, pinned to separate entry-point calls by test_gpu_sgm.py::test_classic_depth_step)
+    stepped on that rig's pair, and the matcher's maps equal the restatement end to end."""
     H, W = 48, 64
     rng = np.random.default_rng(11 + with_maps)
     Qs = np.stack([calib_Q * s for s in (1.0, 2.0, 0.5)])
@@ -309,7 +337,8 @@ def test_classic_depth_batch_step(calib_Q, mode, with_maps):
 
 
 def test_step_launch_count_does_not_depend_on_n(calib_Q):
-    """The entry points a step calls, counted through the call hook: the same list for 1 and for 3 streams."""
+    """The entry points a step calls, counted through the call hook: the same list for 1 and for 3 streams, and for
+    a ClassicDepth."""
     H, W = 24, 40
     rng = np.random.default_rng(3)
     calls = []
@@ -323,8 +352,13 @@ def test_step_launch_count_does_not_depend_on_n(calib_Q):
             calls.clear()
             batch.step(_dev(f), _dev(f))
             seen.append(list(calls))
+        one = sgm.ClassicDepth(Q=calib_Q, **MATCHER_KW)
+        one.step(_dev(f[0]), _dev(f[0]))
+        calls.clear()
+        one.step(_dev(f[0]), _dev(f[0]))
+        seen.append(list(calls))
     finally:
         L.set_call_hook(None)
     torch.cuda.synchronize()
-    assert seen[0] == seen[1] == ["sd_sgm_gray", "sd_sgm_gray", "sd_sgm_compute_n", "sd_sgm_post_n", "sd_sgm_center_n",
-                                  "sd_live_compose_n"]
+    assert seen[0] == seen[1] == seen[2] == ["sd_sgm_gray", "sd_sgm_gray", "sd_sgm_compute_n", "sd_sgm_post_n",
+                                             "sd_sgm_center_n", "sd_live_compose_n"]

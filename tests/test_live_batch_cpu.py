@@ -198,6 +198,68 @@ def test_one_image_size():
     assert live.LiveDepthBatch(M(), 2, (48, 32), rectification=[_rect(), _rect()]).image_size == (40, 30)
 
 
+def test_stream_rectification():
+    """What LiveDepthBatch and ClassicDepthBatch both make of their rectification argument."""
+    assert live.stream_rectification(None, 3) == (None, True, None)
+    r = _rect()
+    rects, shared, size = live.stream_rectification(r, 3)
+    assert shared and size == (40, 30) and len(rects) == 3 and all(x is r for x in rects)
+    three = [_rect(), _rect(), _rect()]
+    for seq in (three, tuple(three)):
+        rects, shared, size = live.stream_rectification(seq, 3)
+        assert not shared and size == (40, 30) and all(x is y for x, y in zip(rects, three))
+    rects, shared, _ = live.stream_rectification([r], 1)  # one stream with a list of one: per-stream maps
+    assert rects == [r] and not shared
+    with pytest.raises(ValueError, match=r"rectification: a sequence must have one entry per stream \(3\), got 2"):
+        live.stream_rectification(three[:2], 3)
+    with pytest.raises(ValueError, match="no None entries"):
+        live.stream_rectification([three[0], None, three[2]], 3)
+    with pytest.raises(ValueError, match=r"one image_size, got \[\(30, 40\), \(40, 30\)\]"):
+        live.stream_rectification([_rect(), _rect((30, 40)), _rect()], 3)
+
+
+def test_upload_maps_checks_and_stacks():
+    rng = np.random.default_rng(0)
+    rects = []
+    for _ in range(2):
+        r = _rect()
+        r.map_l_1 = rng.integers(-100, 100, (30, 40, 2)).astype(np.int16)
+        r.map_l_2 = rng.integers(0, 65536, (30, 40)).astype(np.uint16)  # values above 32767: the bits are kept
+        r.map_r_1 = np.asfortranarray(r.map_l_1 + 1)
+        rects.append(r)
+    m1, m2 = live.upload_maps(rects, "l", 30, 40, "cpu")
+    assert m1.dtype == m2.dtype == live.torch.int16
+    assert tuple(m1.shape) == (2, 30, 40, 2) and tuple(m2.shape) == (2, 30, 40)
+    assert m1.is_contiguous() and m2.is_contiguous()
+    for i, r in enumerate(rects):
+        assert np.array_equal(m1[i].numpy(), r.map_l_1) and np.array_equal(m2[i].numpy().view(np.uint16), r.map_l_2)
+    m1r, _ = live.upload_maps(rects[:1], "r", 30, 40, "cpu")  # the other side, made contiguous
+    assert tuple(m1r.shape) == (1, 30, 40, 2) and np.array_equal(m1r[0].numpy(), rects[0].map_r_1)
+    for attr, bad in (("map_l_1", rects[1].map_l_1.astype(np.int32)), ("map_l_2", rects[1].map_l_2.view(np.int16)),
+                      ("map_l_2", rects[1].map_l_2.astype(np.float32)), ("map_l_1", rects[1].map_l_1[:, :, :1]),
+                      ("map_l_2", rects[1].map_l_2[:29])):
+        good = getattr(rects[1], attr)
+        setattr(rects[1], attr, bad)
+        with pytest.raises(ValueError, match=r"rectification maps: map1 int16 \[H, W, 2\] and map2 uint16 \[H, W\]"):
+            live.upload_maps(rects, "l", 30, 40, "cpu")
+        setattr(rects[1], attr, good)
+    with pytest.raises(ValueError, match="rectification maps"):  # the frame's size, not the maps' own
+        live.upload_maps(rects, "l", 40, 30, "cpu")
+    live.upload_maps(rects, "l", 30, 40, "cpu")
+
+
+def test_colormap_table():
+    assert np.array_equal(live.colormap_table("magma"), live.colormap_lut("magma"))
+    own = np.asfortranarray(np.arange(768, dtype=np.uint8).reshape(256, 3))
+    got = live.colormap_table(own)
+    assert got.flags.c_contiguous and np.array_equal(got, own)
+    for bad in (own.astype(np.float32), own[:255], own.T):
+        with pytest.raises(ValueError, match=r"colormap: a name or a \[256, 3\] uint8 BGR table"):
+            live.colormap_table(bad)
+    with pytest.raises(ValueError, match="unknown colormap"):
+        live.colormap_table("jet")
+
+
 def test_the_other_checks_are_live_depths():
     with pytest.raises(ValueError, match="center_window"):
         live.LiveDepthBatch(M(), 2, (48, 32), center_window=64)

@@ -13,7 +13,7 @@ import pytest
 
 import sgm_ref as R
 from stereo_depth_estimation_amd import _lib as L
-from stereo_depth_estimation_amd import sgm
+from stereo_depth_estimation_amd import live, sgm
 
 H, W, D, BS = 24, 96, 32, 7
 
@@ -176,6 +176,32 @@ def test_reprojection_matrix_handling(golden_dir):
         sgm.ClassicDepth(Q=Q, block_size=6)
     c = sgm.ClassicDepth(Q=Q, num_disparities=64, colormap="inferno")  # no device touched before the first step
     assert c.matcher.num_disparities == 64 and c.center_window == 15
+
+
+def test_classic_depth_is_the_one_stream_batch(golden_dir, monkeypatch):
+    with np.load(golden_dir / "sgm_calib.npz") as d:
+        Q = d["Q"]
+
+    def no_device(*a, **kw):
+        raise AssertionError("the constructor touched the device")
+
+    for name in ("empty", "zeros", "full", "as_tensor"):
+        monkeypatch.setattr(sgm.torch, name, no_device)
+    monkeypatch.setattr(sgm.torch.cuda, "current_device", no_device)
+    monkeypatch.setattr(L, "call", no_device)
+    for bad in (np.stack([Q]), np.stack([Q] * 2)):  # a batch's [n, 4, 4] is not a single rig's matrix
+        with pytest.raises(ValueError, match="Q must be the 4 x 4"):
+            sgm.ClassicDepth(Q=bad)
+    z1, z2 = np.zeros((48, 64, 2), np.int16), np.zeros((48, 64), np.uint16)
+    rect = live.Rectification(z1, z2, z1, z2, (64, 48), 500.0, 0.07)
+    c = sgm.ClassicDepth(rectification=rect, Q=Q.astype(np.float32), center_window=9, mode="hh")
+    assert c.Q.shape == (4, 4) and c.Q.dtype == np.float64 and np.array_equal(c.Q, Q.astype(np.float32))
+    assert c.rectification is rect and c.center_window == 9 and c.matcher.mode == "hh"
+    assert c.device == sgm.torch.device("cuda") and c.device.index is None  # resolved by the first step
+    assert isinstance(c._batch, sgm.ClassicDepthBatch) and c._batch.streams == 1 and c.matcher is c._batch.matcher
+    assert sgm.ClassicBatchResult is sgm.ClassicResult
+    with pytest.raises(RuntimeError, match="before the first step"):
+        c._readout()
 
 
 def test_workspace_bytes_match_the_formula():

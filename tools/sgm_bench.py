@@ -12,8 +12,9 @@ further paths (each one launch that reads C and S and writes S: three volumes, H
 them alone, with top -> down as an adding pass of the same kernel beside them.
 
 --streams N times, in one session and at the same frame, parameters and protocol, ClassicDepthBatch(N) (N rigs through
-one launch per stage) against N ClassicDepth objects stepped in turn, and the batch's entry points alone (the matcher
-as one stage: its kernels have no batched entry points of their own; a kernel trace of this tool splits it).
+one launch per stage) against N ClassicDepth objects (each a batch of one) stepped in turn, and the batch's entry
+points alone (the matcher as one stage: its kernels have no batched entry points of their own; a kernel trace of this
+tool splits it).
 
     python tools/sgm_bench.py --frames 640x480 --num-disparities 128 --block-size 7 --mode hh --json out.json
     python tools/sgm_bench.py --streams 8 --mode 3way
@@ -109,8 +110,9 @@ def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str 
     q = res.disparity_q4
     out["valid_fraction"] = float((q[:, D:] != cd.matcher.invalid_value).float().mean())
 
-    # each stage alone, back-to-back launches on the frame's own buffers
-    b, m, s = cd._buf, cd.matcher, L.stream_handle(dev)
+    # each stage alone, back-to-back launches on the frame's own buffers ([1] of every buffer: stream 0's slice starts
+    # at the base pointer), through the single-stream entry points
+    b, m, s = cd._batch._buf, cd.matcher, L.stream_handle(dev)
     H, W, P = hc, wc, hc * wc
     vol = (2 * P * D + 255) // 256 * 256
     ws = m.workspace(dev, H, W)
@@ -121,6 +123,7 @@ def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str 
     fld, frd = b["frames"][0][0], b["frames"][0][1]
     gl, gr = b["gray"][0], b["gray"][1]
     q_tmp = torch.empty_like(q)
+    Q = np.ascontiguousarray(cd.Q)
     agg = (C, H, W, m.min_disparity, D, m.P1, m.P2)
     stages = {
         "rectify (x2)": lambda: [L.call("sd_live_rectify", f.data_ptr(), H, W, b[f"m1{k}"].data_ptr(),
@@ -140,7 +143,7 @@ def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str 
            for dy, dx in (((1, 0),) + EXTRA_PATHS[mode] if mode != "3way" else ())},
         "speckle": lambda: (q_tmp.copy_(q), L.call("sd_sgm_speckle", q_tmp.data_ptr(), H, W, m.invalid_value,
                                                    m.speckle_window_size, m.speckle_range, sw, s)),
-        "post": lambda: L.call("sd_sgm_post", q.data_ptr(), H, W, cd.Q.ctypes.data, b["disp"].data_ptr(),
+        "post": lambda: L.call("sd_sgm_post", q.data_ptr(), H, W, Q.ctypes.data, b["disp"].data_ptr(),
                                b["z"].data_ptr(), b["code"].data_ptr(), b["minmax"].data_ptr(), s),
         "center": lambda: L.call("sd_sgm_center", b["z"].data_ptr(), H, W, cd.center_window, b["center"].data_ptr(), s),
         "compose": lambda: L.call("sd_live_compose", b["code"].data_ptr(), b["lut"].data_ptr(), b["vis"].data_ptr(),
@@ -218,7 +221,7 @@ def bench_streams(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mo
     # the batch's entry points alone, back-to-back launches on the step's own buffers
     b, s = batch._buf, L.stream_handle(dev)
     H, W = hc, wc
-    ws = m.workspace_batch(dev, n, H, W)
+    ws = m.workspace(dev, H, W, n)
     frames = b["frames"][0]
     q_tmp = torch.empty_like(q)
     sw = torch.empty(n * L.call("sd_sgm_speckle_ws_bytes", H, W), dtype=torch.uint8, device=dev)
