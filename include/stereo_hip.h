@@ -682,6 +682,40 @@ int sd_disp_export(const float* disp, const float* logvar, int batch, int H, int
 int sd_write_png_batch(const char* const* paths, int n, int H, int W, const uint8_t* rgb, int level, int threads,
                        char* err, int errlen);
 
+/* ---- coloured point clouds (stereo_depth_estimation_amd/cloud.py; cv2.reprojectImageTo3D of depth_live.py:164 with
+ * all three coordinates, masked and packed) ----
+ * n streams (1..64) of one size H x W, stream-major: disp f32 [n][H][W]; color u8 [n][H][W][3] or NULL, BGR when
+ * color_bgr is 1, RGB when 0; Qdev a DEVICE array f64 [n][16], one row-major 4 x 4 matrix per stream, as sd_sgm_post_n
+ * takes it; z_min <= z_max as float32, +-inf for no bound, NaN refused; stride 1..64.
+ *   value  a pixel whose disp is finite and > 0. d = (double)disp, R_r = ((Q[r][0] x + Q[r][1] y) + Q[r][2] d) + Q[r][3]
+ *          in fp64, every operation rounded on its own; X, Y, Z = float32(R_0 / R_3), float32(R_1 / R_3),
+ *          float32(R_2 / R_3). Z is bit-equal to sd_sgm_post's z on the same disparity.
+ *   kept   a value whose X, Y and Z are finite as float32 and z_min <= Z <= z_max (compared in float32)
+ *   xyz    f32 [n][H][W][3] or NULL: the organised cloud, the point of a kept pixel and three NaNs elsewhere; stride
+ *          and cap do not apply to it
+ *   points [n][cap] records of 16 bytes, 16-B aligned, or NULL: float32 x, y, z; uint8 red, green, blue, alpha = 255
+ *          (little-endian; white without color). Stream i holds its kept pixels with x % stride == 0 && y % stride == 0
+ *          in ascending (y, x) order (NumPy's boolean-mask order). count u32 [n]: their number, whether or not it
+ *          exceeds cap; only the first min(count[i], cap) records are written, and no other byte of points is touched.
+ * The same inputs give the same bytes on every run, and stream i's bytes do not depend on n or on its neighbours: the
+ * order comes from a prefix sum (count per 1024-pixel tile, scan of the tile counts per stream, scatter), never from
+ * atomics, and no block waits for another. Three launches with points, one with xyz alone, whatever n is. One of xyz /
+ * points at least; points need count, cap >= 1 and work: sd_cloud_ws_bytes(n, H, W, stride) bytes, 4-B aligned, needs no
+ * clearing (-1 for n outside 1..64, non-positive sizes, H * W >= 2^31, stride outside 1..64; host only). Arguments are
+ * checked before any launch; no allocation, no synchronisation, graph-capturable. */
+long long sd_cloud_ws_bytes(int n, int H, int W, int stride);
+int sd_cloud_build_n(int n, const float* disp, const uint8_t* color, int color_bgr, int H, int W, const double* Qdev,
+                     float z_min, float z_max, int stride, float* xyz, void* points, long long cap, unsigned* count,
+                     void* work, sd_stream s);
+/* Host only: n clouds -> binary little-endian PLY files. points: [n][cap] records as sd_cloud_build_n writes them (in
+ * host memory), counts u32 [n]. File i is the header
+ *   ply / format binary_little_endian 1.0 / element vertex N / property float x / property float y / property float z /
+ *   property uchar red / property uchar green / property uchar blue / property uchar alpha / end_header
+ * (one line each, '\n' ends), N = min(counts[i], cap), followed by the first N records of slice i verbatim; N = 0 is a
+ * valid file. At most min(threads, 16) threads; file handling and return codes as sd_write_png_batch. */
+int sd_write_ply_batch(const char* const* paths, int n, const void* points, long long cap, const unsigned* counts,
+                       int threads, char* err, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@
     python -m stereo_depth_estimation_amd.predict --checkpoint best.pt \\
         (--dataset-root DIR | --left-dir DIR --right-dir DIR) [--output-root DIR] \\
         [--height H --width W] [--precision fp32|bf16|fp8] [--base-channels 32] [--batch-size 32] [--max-samples 0] \\
-        [--write-sigma] [--png-level 1] [--read-threads 16] [--device cuda]
+        [--write-sigma] [--png-level 1] [--read-threads 16] [--device cuda] \\
+        [--write-ply (--calibration FILE.npz | --focal-px F --baseline-m B [--cx X --cy Y]) \\
+         [--ply-stride 1] [--ply-min-depth M] [--ply-max-depth M]]
 
 Runs a trained checkpoint (``cli.save_checkpoint``'s format, or the reference's) over frames on disk and
 
@@ -22,6 +24,11 @@ other PNG kinds by PIL), a side stream copies them up and runs ``sd_stereo_prepr
 both heads at batch n and ``sd_disp_export``, 3 bytes per pixel (6 with sigma) plus the metric rows come back, and the
 native PNG writer writes the files; the decode of batch i+1, the device work of batch i and the writing of batch i-1
 overlap. Every sample is written every time (no skip rule), each file under a temporary name and renamed.
+
+``--write-ply`` adds ``<name>.ply`` beside each disparity file: the coloured point cloud of the sample at the frame's own
+resolution (``sd_cloud_build_n`` on sd_disp_export's upsampled disparity and the left frame; cloud.py), its records and
+counts riding the same copy back and the same writer thread. The geometry is a calibration file (keys ``Q`` and
+``image_size``; ``cloud.rescale_Q`` for frames of another size) or an ideal rig in pixels of the frames.
 
 ``--precision fp8``: the first batch is the calibration forward (its activations set the static e4m3 scales of all
 later batches), and the scales are per tensor over the batch, as in ``LiveDepthBatch``; there are no per-sample scales.
@@ -60,6 +67,90 @@ class PredictItem:
     relpath: Path
 
 
+@dataclass(frozen=True)
+class CloudOptions:
+    """What ``--write-ply`` needs: the geometry and the selection of points. The geometry is either a calibration (its
+    4 x 4 ``Q`` and the ``image_size`` = (width, height) it holds for; frames of another size get ``rescale_Q``) or an
+    ideal rectified rig in pixels of the frames themselves (``focal_px``, ``baseline_m``, the principal point ``cx``,
+    ``cy``, by default the frame centre ((Ws - 1) / 2, (Hs - 1) / 2))."""
+    Q: tuple | None = None
+    image_size: tuple | None = None
+    focal_px: float | None = None
+    baseline_m: float | None = None
+    cx: float | None = None
+    cy: float | None = None
+    stride: int = 1
+    z_range: tuple = (-math.inf, math.inf)
+
+    def matrix(self, Hs: int, Ws: int) -> np.ndarray:
+        """The reprojection matrix for frames of Hs x Ws, float64 [4, 4]."""
+        from .cloud import pinhole_Q, rescale_Q
+
+        if self.Q is not None:
+            Q = np.asarray(self.Q, dtype=np.float64).reshape(4, 4)
+            if self.image_size is None or tuple(self.image_size) == (Ws, Hs):
+                return Q
+            return rescale_Q(Q, Ws / self.image_size[0], Hs / self.image_size[1])
+        return pinhole_Q(self.focal_px, self.baseline_m, (Ws - 1) / 2 if self.cx is None else self.cx,
+                         (Hs - 1) / 2 if self.cy is None else self.cy)
+
+    def describe(self) -> dict:
+        """The cloud arguments as ``predict_meta.json`` records them."""
+        finite = lambda v: float(v) if math.isfinite(v) else None  # noqa: E731
+        return {"write_ply": True,
+                "ply_calibration_Q": [float(v) for v in self.Q] if self.Q is not None else None,
+                "ply_calibration_image_size": [int(v) for v in self.image_size] if self.image_size else None,
+                "focal_px": self.focal_px, "baseline_m": self.baseline_m, "cx": self.cx, "cy": self.cy,
+                "ply_stride": int(self.stride), "ply_min_depth": finite(self.z_range[0]),
+                "ply_max_depth": finite(self.z_range[1])}
+
+
+def cloud_options(write_ply: bool = False, output_root=None, calibration=None, focal_px=None, baseline_m=None, cx=None, cy=None,
+                  ply_stride: int = 1, ply_min_depth=None, ply_max_depth=None) -> CloudOptions | None:
+    """The ``--write-ply`` flags checked and gathered; None without the flag (the other flags then must be unset)."""
+    from .cloud import MAX_STRIDE, pinhole_Q, z_bounds
+    from .sgm import reprojection_rows
+
+    given = [k for k, v in (("--calibration", calibration), ("--focal-px", focal_px), ("--baseline-m", baseline_m),
+                            ("--cx", cx), ("--cy", cy), ("--ply-min-depth", ply_min_depth),
+                            ("--ply-max-depth", ply_max_depth)) if v is not None]
+    if not write_ply:
+        if given or int(ply_stride) != 1:
+            raise ValueError(f"{', '.join(given) or '--ply-stride'}: only with --write-ply.")
+        return None
+    if output_root is None:
+        raise ValueError("--write-ply needs --output-root.")
+    if calibration is not None and (focal_px is not None or baseline_m is not None or cx is not None or cy is not None):
+        raise ValueError("--write-ply: give either --calibration or --focal-px / --baseline-m, not both.")
+    if not 1 <= int(ply_stride) <= MAX_STRIDE:
+        raise ValueError(f"--ply-stride must be in [1, {MAX_STRIDE}], got: {ply_stride}")
+    try:
+        z_range = z_bounds((-math.inf if ply_min_depth is None else ply_min_depth,
+                            math.inf if ply_max_depth is None else ply_max_depth))
+    except ValueError as e:
+        raise ValueError(f"--ply-min-depth / --ply-max-depth: {e}") from None
+    if calibration is not None:
+        with np.load(Path(calibration).expanduser()) as d:
+            if "Q" not in d.files or "image_size" not in d.files:
+                raise ValueError(f"--calibration {calibration}: the file needs the keys Q and image_size.")
+            Q = reprojection_rows(d["Q"])
+            size = tuple(int(v) for v in np.asarray(d["image_size"]).reshape(-1)[:2])
+        if len(size) != 2 or min(size) < 1:
+            raise ValueError(f"--calibration {calibration}: image_size must be (width, height), got {size}")
+        return CloudOptions(Q=tuple(Q.reshape(-1)), image_size=size, stride=int(ply_stride), z_range=z_range)
+    if focal_px is None or baseline_m is None:
+        raise ValueError("--write-ply needs a geometry: --calibration FILE.npz, or --focal-px and --baseline-m.")
+    if (cx is None) != (cy is None):
+        raise ValueError("--cx and --cy: give both or neither (default: the frame centre).")
+    pinhole_Q(focal_px, baseline_m, 0.0 if cx is None else cx, 0.0 if cy is None else cy)  # checks the numbers
+    return CloudOptions(focal_px=float(focal_px), baseline_m=float(baseline_m), cx=None if cx is None else float(cx),
+                        cy=None if cy is None else float(cy), stride=int(ply_stride), z_range=z_range)
+
+
+def ply_relpath(relpath: Path) -> Path:
+    return relpath.with_suffix(".ply")
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Predict disparity files from stereo pairs on disk and evaluate them.")
     p.add_argument("--checkpoint", type=str, required=True, help="Checkpoint of the training CLI (or the reference's).")
@@ -77,6 +168,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--png-level", type=int, default=1, help="zlib level of the PNG writer, 0..9.")
     p.add_argument("--read-threads", type=int, default=16, help="Host threads of the PNG reader and of the writer.")
     p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--write-ply", action="store_true",
+                   help="Also write <name>.ply, the coloured point cloud (needs --output-root and a geometry).")
+    p.add_argument("--calibration", type=str, default=None, help="Calibration .npz with the keys Q and image_size.")
+    p.add_argument("--focal-px", type=float, default=None, help="Focal length in pixels of the frames (with --baseline-m).")
+    p.add_argument("--baseline-m", type=float, default=None, help="Baseline of the rig in metres.")
+    p.add_argument("--cx", type=float, default=None, help="Principal point x (default: the frame centre).")
+    p.add_argument("--cy", type=float, default=None, help="Principal point y (default: the frame centre).")
+    p.add_argument("--ply-stride", type=int, default=1, help="Keep every n-th pixel in x and y, 1..64.")
+    p.add_argument("--ply-min-depth", type=float, default=None, help="Smallest kept Z in metres (default: no bound).")
+    p.add_argument("--ply-max-depth", type=float, default=None, help="Largest kept Z in metres (default: no bound).")
     return p
 
 
@@ -149,6 +250,7 @@ class Predictor:
             raise RuntimeError(f"Predictor runs only on a HIP device (no CPU path); the model is on {self.device}")
         self._calibrated = False
         self._buf: dict = {}
+        self._cloud_buf: dict = {}
 
     def _buffers(self, n: int, Hs: int, Ws: int, sigma: bool) -> dict:
         """Device buffers for batches of up to n samples of one source size (grown, never shrunk)."""
@@ -170,12 +272,39 @@ class Predictor:
             self._buf[key] = b
         return b
 
+    def _cloud_buffers(self, n: int, Hs: int, Ws: int, cloud: CloudOptions) -> dict:
+        """Device buffers of the point-cloud stage for batches of up to n samples of one source size (grown, never
+        shrunk); the reprojection matrix of this size is uploaded when they are made."""
+        from .cloud import MAX_STREAMS, lattice_size
+
+        key = (Hs, Ws, cloud)
+        b = self._cloud_buf.get(key)
+        if b is None or b["n"] < n:
+            dev = self.device
+            nb = max(n, b["n"]) if b is not None else n
+            cap = lattice_size(Hs, Ws, cloud.stride)
+            streams = min(nb, MAX_STREAMS)  # per sd_cloud_build_n call: larger batches take several
+            Q = np.ascontiguousarray(np.broadcast_to(cloud.matrix(Hs, Ws).reshape(1, 16), (streams, 16)))
+            with torch.inference_mode(False):
+                b = {"n": nb, "cap": cap, "streams": streams,
+                     "disp_up": torch.empty(nb, Hs, Ws, device=dev),
+                     "points": torch.empty(nb, cap, 16, device=dev, dtype=torch.uint8),
+                     "counts": torch.empty(nb, device=dev, dtype=torch.int32),
+                     "Q": torch.as_tensor(Q).to(dev),
+                     "work": torch.empty(L.call("sd_cloud_ws_bytes", streams, Hs, Ws, cloud.stride) // 4, device=dev,
+                                         dtype=torch.int32)}
+            self._cloud_buf[key] = b
+        return b
+
     def run(self, left_u8: torch.Tensor, right_u8: torch.Tensor, gt_rgb: torch.Tensor | None = None,
-            sigma: bool = False, images: bool = True) -> dict:
+            sigma: bool = False, images: bool = True, cloud: CloudOptions | None = None) -> dict:
         """left_u8, right_u8 (and gt_rgb, the RGB24 ground truth): contiguous uint8 [n,Hs,Ws,3] on the model's device.
         Queues the batch on the current stream and returns device tensors without synchronising: ``disp_rgb`` and
         ``sigma_rgb`` uint8 [n,Hs,Ws,3] (None unless asked for), ``rows`` float64 [n,8] (None without gt_rgb). They are
-        views of buffers the next ``run`` at this source size overwrites."""
+        views of buffers the next ``run`` at this source size overwrites. With ``cloud`` the result also holds
+        ``disp_up`` float32 [n,Hs,Ws] (sd_disp_export's), ``points`` uint8 [n,cap,16] and ``counts`` int32 [n] (the
+        bits of uint32): sd_cloud_build_n on disp_up and the left frame (RGB) at the frame's own resolution, cap the
+        lattice size."""
         n, Hs, Ws = (int(v) for v in left_u8.shape[:3])
         for name, t in (("left_u8", left_u8), ("right_u8", right_u8), ("gt_rgb", gt_rgb)):
             if t is None:
@@ -184,10 +313,11 @@ class Predictor:
                     or t.device != self.device):
                 raise ValueError(f"Predictor.run: {name} must be a contiguous uint8 tensor of {(n, Hs, Ws, 3)} on "
                                  f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        if not (images or gt_rgb is not None):
+        if not (images or gt_rgb is not None or cloud is not None):
             raise ValueError("Predictor.run: neither images nor metrics requested")
         sigma = bool(sigma and images)
         b = self._buffers(n, Hs, Ws, sigma)
+        cb = self._cloud_buffers(n, Hs, Ws, cloud) if cloud is not None else None
         H, W = self.H, self.W
         with torch.cuda.device(self.device):
             s = L.stream_handle(self.device)
@@ -204,10 +334,21 @@ class Predictor:
             self._calibrated = True
             L.call("sd_disp_export", disp.data_ptr(), logvar.data_ptr() if sigma else None, n, H, W,
                    gt_rgb.data_ptr() if gt_rgb is not None else None, Hs, Ws,
-                   b["disp_rgb"].data_ptr() if images else None, b["sigma_rgb"].data_ptr() if sigma else None, None,
+                   b["disp_rgb"].data_ptr() if images else None, b["sigma_rgb"].data_ptr() if sigma else None,
+                   cb["disp_up"].data_ptr() if cb is not None else None,
                    b["rows"].data_ptr() if gt_rgb is not None else None, b["work"].data_ptr(), s)
-        return {"disp_rgb": b["disp_rgb"][:n] if images else None, "sigma_rgb": b["sigma_rgb"][:n] if sigma else None,
-                "rows": b["rows"][:n] if gt_rgb is not None else None}
+            if cb is not None:
+                px, cap = Hs * Ws, cb["cap"]
+                for c0 in range(0, n, cb["streams"]):
+                    L.call("sd_cloud_build_n", min(cb["streams"], n - c0), cb["disp_up"].data_ptr() + c0 * px * 4,
+                           left_u8.data_ptr() + c0 * px * 3, 0, Hs, Ws, cb["Q"].data_ptr(), cloud.z_range[0],
+                           cloud.z_range[1], cloud.stride, None, cb["points"].data_ptr() + c0 * cap * 16, cap,
+                           cb["counts"].data_ptr() + c0 * 4, cb["work"].data_ptr(), s)
+        res = {"disp_rgb": b["disp_rgb"][:n] if images else None, "sigma_rgb": b["sigma_rgb"][:n] if sigma else None,
+               "rows": b["rows"][:n] if gt_rgb is not None else None}
+        if cb is not None:
+            res.update(disp_up=cb["disp_up"][:n], points=cb["points"][:n], counts=cb["counts"][:n])
+        return res
 
 
 class PredictPipeline:
@@ -218,8 +359,11 @@ class PredictPipeline:
     device buffers are made once per source size (and slot) and reused by every later batch of that size."""
 
     def __init__(self, predictor: Predictor, batch_size: int, has_gt: bool, images: bool, sigma: bool,
-                 png_level: int = 1, read_threads: int = 16):
+                 png_level: int = 1, read_threads: int = 16, cloud: CloudOptions | None = None):
         self.p, self.bmax, self.has_gt, self.images, self.sigma = predictor, batch_size, has_gt, images, sigma and images
+        self.cloud = cloud
+        self._ply = [{}, {}]  # per slot: source size -> (records [bmax,cap,16], counts [bmax]) pinned
+        self.point_counts: list = []  # with cloud: the counts (uint32 [n]) of every written batch, in order
         self.level, self.threads = png_level, read_threads
         self.device = predictor.device
         self.stream = torch.cuda.Stream(self.device)
@@ -242,6 +386,15 @@ class PredictPipeline:
             self._out[slot][hw] = (img() if self.images else None, img() if self.sigma else None,
                                    torch.zeros(self.bmax, ROW, dtype=torch.float64).pin_memory())
         return self._out[slot][hw]
+
+    def _pinned_ply(self, slot: int, hw):
+        if hw not in self._ply[slot]:
+            from .cloud import lattice_size
+
+            cap = lattice_size(*hw, self.cloud.stride)
+            self._ply[slot][hw] = (torch.empty(self.bmax, cap, 16, dtype=torch.uint8).pin_memory(),
+                                   torch.zeros(self.bmax, dtype=torch.int32).pin_memory())
+        return self._ply[slot][hw]
 
     def decode(self, slot: int, hw, items) -> list[tuple]:
         """Source frames of one batch as parts (left, right[, ground truth]), each uint8 [n,Hs,Ws,3] pinned and of one
@@ -267,7 +420,8 @@ class PredictPipeline:
                 for run in parts]
 
     def device_work(self, slot: int, parts):
-        """Queues one batch on the side stream. Returns (event, [(n, (Hs, Ws), pinned disp_rgb, sigma_rgb, rows)])."""
+        """Queues one batch on the side stream. Returns (event, [(n, (Hs, Ws), pinned disp_rgb, sigma_rgb, rows,
+        records, counts)]); the last two are None without a cloud."""
         dev, outs = self.device, []
         with torch.cuda.stream(self.stream):
             off: dict = {}
@@ -280,7 +434,8 @@ class PredictPipeline:
                 up = tuple(d[:n] for d in self._dev[hw])
                 for d, h in zip(up, part):
                     d.copy_(h, non_blocking=True)
-                res = self.p.run(up[0], up[1], up[2] if self.has_gt else None, sigma=self.sigma, images=self.images)
+                res = self.p.run(up[0], up[1], up[2] if self.has_gt else None, sigma=self.sigma, images=self.images,
+                                 cloud=self.cloud)
                 o = off.get(hw, 0)  # parts of one size within a batch share the slot's buffers
                 off[hw] = o + n
                 h_disp, h_sigma, h_rows = self._pinned_out(slot, hw)
@@ -292,17 +447,30 @@ class PredictPipeline:
                     h_sigma[o:o + n].copy_(res["sigma_rgb"], non_blocking=True)
                 if self.has_gt:
                     h_rows[o:o + n].copy_(res["rows"], non_blocking=True)
+                h_pts = h_cnt = None
+                if self.cloud is not None:  # the whole block and the counts ride the same copy-back
+                    h_pts, h_cnt = (t[o:o + n] for t in self._pinned_ply(slot, hw))
+                    h_pts.copy_(res["points"], non_blocking=True)
+                    h_cnt.copy_(res["counts"], non_blocking=True)
                 outs.append((n, hw, h_disp[o:o + n] if self.images else None,
-                             h_sigma[o:o + n] if self.sigma else None, h_rows[o:o + n]))
+                             h_sigma[o:o + n] if self.sigma else None, h_rows[o:o + n], h_pts, h_cnt))
             ev = torch.cuda.Event()
             ev.record(self.stream)
         return ev, outs
 
-    def write(self, paths, sigma_paths, ev: torch.cuda.Event, outs) -> np.ndarray:
-        """Waits for the batch, writes its files (paths: one per sample in batch order, or None) and returns its rows."""
+    def write(self, paths, sigma_paths, ev: torch.cuda.Event, outs, ply_paths=None) -> np.ndarray:
+        """Waits for the batch, writes its files (paths: one per sample in batch order, or None) and returns its rows.
+        With a cloud, the batch's point counts are appended to ``point_counts``."""
+        from .cloud import write_ply_batch
+
         ev.synchronize()
         k, rows = 0, []
-        for n, hw, h_disp, h_sigma, h_rows in outs:
+        for n, hw, h_disp, h_sigma, h_rows, h_pts, h_cnt in outs:
+            if h_pts is not None:
+                counts = h_cnt.numpy().view(np.uint32).copy()
+                if ply_paths is not None:
+                    write_ply_batch(ply_paths[k:k + n], h_pts, counts, self.threads)
+                self.point_counts.append(counts)
             if paths is not None and h_disp is not None:
                 write_png_batch(paths[k:k + n], hw, h_disp, self.level, self.threads)
             if sigma_paths is not None and h_sigma is not None:
@@ -323,7 +491,8 @@ def load_model(checkpoint, precision: str = "fp32", base_channels: int = 32, dev
 
 
 def _run(items: list[PredictItem], mode: str, source: str, described: dict, checkpoint, model, output_root, height,
-         width, precision, base_channels, batch_size, max_samples, write_sigma, png_level, read_threads, device) -> dict:
+         width, precision, base_channels, batch_size, max_samples, write_sigma, png_level, read_threads, device,
+         ply: dict | None = None) -> dict:
     dev = _resolve_device(device)
     if batch_size < 1:
         raise ValueError(f"--batch-size must be >= 1, got: {batch_size}")
@@ -334,6 +503,7 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
         raise ValueError("Nothing to do: no ground truth to evaluate against and no --output-root to write to.")
     if write_sigma and output_root is None:
         raise ValueError("--write-sigma needs --output-root.")
+    cloud = cloud_options(output_root=output_root, **(ply or {}))
     if max_samples > 0:
         items = items[:max_samples]
     if not items:
@@ -360,7 +530,8 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
 
     batches = plan_batches(items, batch_size)
     predictor = Predictor(model, (width, height))
-    pipe = PredictPipeline(predictor, batch_size, has_gt, out_root is not None, write_sigma, png_level, read_threads)
+    pipe = PredictPipeline(predictor, batch_size, has_gt, out_root is not None, write_sigma, png_level, read_threads,
+                           cloud)
     events, writes, held = [None, None], [None, None], [None, None]
     done: list = []  # (batch's items, future of its rows) in order
     try:
@@ -379,7 +550,8 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
                 held[k] = parts  # pinned frames stay alive until their copies are done (the slot's next turn)
                 paths = [out_root / it.relpath for it in its] if out_root is not None else None
                 spaths = [out_root / sigma_relpath(it.relpath) for it in its] if (out_root and write_sigma) else None
-                writes[k] = writer.submit(pipe.write, paths, spaths, events[k], outs)
+                ppaths = [out_root / ply_relpath(it.relpath) for it in its] if (out_root and cloud) else None
+                writes[k] = writer.submit(pipe.write, paths, spaths, events[k], outs, ppaths)
                 done.append((its, writes[k]))
             rows = [(its, w.result()) for its, w in done]
     finally:
@@ -407,14 +579,23 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
         "elapsed_seconds": elapsed,
         "created_at_unix": time.time(),
     }
+    points = None
+    if cloud is not None:  # one .ply per sample beside its disparity file (not counted in num_written)
+        points = np.concatenate(pipe.point_counts).astype(np.int64)
+        meta.update(cloud.describe(), points=int(points.sum()))
     if has_gt:
         all_rows = np.concatenate([r for _, r in rows])
         meta.update(aggregate_rows(all_rows))
         if out_root is not None:
             with open(out_root / "metrics.jsonl", "w", encoding="utf-8") as f:
+                k = 0
                 for (its, r) in rows:
                     for it, row in zip(its, r):
-                        f.write(json.dumps({"sample": it.relpath.as_posix(), **metrics_from_row(row)}) + "\n")
+                        rec = {"sample": it.relpath.as_posix(), **metrics_from_row(row)}
+                        if points is not None:
+                            rec["points"] = int(points[k])
+                        f.write(json.dumps(rec) + "\n")
+                        k += 1
     if out_root is not None:
         (out_root / "predict_meta.json").write_text(json.dumps(meta, indent=2), encoding="utf-8")
     print(json.dumps(meta))
@@ -423,22 +604,26 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
 
 def predict_dataset(checkpoint, dataset_root, output_root=None, *, model=None, height=None, width=None,
                     precision: str = "fp32", base_channels: int = 32, batch_size: int = 32, max_samples: int = 0,
-                    write_sigma: bool = False, png_level: int = 1, read_threads: int = 16, device="cuda") -> dict:
+                    write_sigma: bool = False, png_level: int = 1, read_threads: int = 16, device="cuda", **ply) -> dict:
     """A FoundationStereo tree: disparity files under output_root (if given) and the metrics against the tree's ground
     truth. ``model``: a StereoUNet to use instead of loading ``checkpoint`` (height and width are then required).
-    Returns the dict that is also written to ``predict_meta.json`` and printed as one JSON line."""
+    Returns the dict that is also written to ``predict_meta.json`` and printed as one JSON line. ``ply``: the keywords
+    of ``cloud_options`` (write_ply=True, then calibration=FILE or focal_px= and baseline_m=, optionally cx=, cy=,
+    ply_stride=, ply_min_depth=, ply_max_depth=): also ``<scene>/<frame>.ply``, the coloured point cloud of each sample
+    at the frame's own resolution."""
     _resolve_device(device)
     root = Path(dataset_root).expanduser().resolve()
     items = dataset_items(root)
     return _run(items, "dataset", str(root), {"dataset_root": str(root)}, checkpoint, model, output_root,
                 height, width, precision, base_channels, batch_size, max_samples, write_sigma, png_level, read_threads,
-                device)
+                device, ply)
 
 
 def predict_pairs(checkpoint, left_dir, right_dir, output_root, *, model=None, height=None, width=None,
                   precision: str = "fp32", base_channels: int = 32, batch_size: int = 32, max_samples: int = 0,
-                  write_sigma: bool = False, png_level: int = 1, read_threads: int = 16, device="cuda") -> dict:
-    """Two directories of frames paired by stem: ``<output_root>/<stem>.png``, no metrics."""
+                  write_sigma: bool = False, png_level: int = 1, read_threads: int = 16, device="cuda", **ply) -> dict:
+    """Two directories of frames paired by stem: ``<output_root>/<stem>.png`` (and ``<stem>.ply`` with the ``ply``
+    keywords of ``predict_dataset``), no metrics."""
     _resolve_device(device)
     if output_root is None:
         raise ValueError("Nothing to do: no ground truth to evaluate against and no --output-root to write to.")
@@ -446,7 +631,7 @@ def predict_pairs(checkpoint, left_dir, right_dir, output_root, *, model=None, h
     items = pair_by_stem(left, right)
     return _run(items, "pairs", f"{left} + {right}", {"left_dir": str(left), "right_dir": str(right)}, checkpoint,
                 model, output_root, height, width, precision, base_channels, batch_size, max_samples,
-                write_sigma, png_level, read_threads, device)
+                write_sigma, png_level, read_threads, device, ply)
 
 
 def main(argv=None) -> dict:
@@ -459,6 +644,11 @@ def main(argv=None) -> dict:
     common = dict(height=a.height, width=a.width, precision=a.precision, base_channels=a.base_channels,
                   batch_size=a.batch_size, max_samples=a.max_samples, write_sigma=a.write_sigma, png_level=a.png_level,
                   read_threads=a.read_threads, device=a.device)
+    if a.write_ply or any(v is not None for v in (a.calibration, a.focal_px, a.baseline_m, a.cx, a.cy, a.ply_min_depth,
+                                                  a.ply_max_depth)) or a.ply_stride != 1:
+        common.update(write_ply=a.write_ply, calibration=a.calibration, focal_px=a.focal_px, baseline_m=a.baseline_m,
+                      cx=a.cx, cy=a.cy, ply_stride=a.ply_stride, ply_min_depth=a.ply_min_depth,
+                      ply_max_depth=a.ply_max_depth)
     if a.dataset_root is not None:
         return predict_dataset(a.checkpoint, a.dataset_root, a.output_root, **common)
     return predict_pairs(a.checkpoint, a.left_dir, a.right_dir, a.output_root, **common)

@@ -241,6 +241,8 @@ class ClassicDepthBatch:
         self.device = torch.device(device)
         self._buf = None
         self._key = None
+        self._last_rect_left = None  # the last step's rectified left frames: the colours of cloud()
+        self._cloud_builder = None
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, H: int, W: int):
@@ -330,6 +332,7 @@ class ClassicDepthBatch:
             L.call("sd_sgm_center_n", n, b["z"].data_ptr(), H, W, self.center_window, b["center"].data_ptr(), s)
             L.call("sd_live_compose_n", n, b["code"].data_ptr(), b["lut"].data_ptr(), b["vis"].data_ptr(), None, None,
                    None, None, None, None, H, W, H, W, 0, s)
+        self._last_rect_left = rect_l
         return ClassicResult(self, disparity_q4=b["q"], disparity=b["disp"], depth_m=b["z"], rect_left=rect_l,
                              rect_right=rect_r, disp_vis=b["vis"])
 
@@ -340,6 +343,20 @@ class ClassicDepthBatch:
         b["center_host"].copy_(b["center"], non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         return b["center_host"].numpy().copy()
+
+    def cloud(self, z_range=(-float("inf"), float("inf")), stride: int = 1, organized: bool = False):
+        """The coloured point clouds of the last step (cloud.PointCloudBuilder.build on its disparity, rect_left as BGR
+        colours and the object's Q): a cloud.CloudResult of n streams. Launches only; the builder and its buffers are
+        made at the first call. step() itself runs nothing of this."""
+        if self._buf is None or self._last_rect_left is None:
+            raise RuntimeError("cloud() before the first step")
+        if self._cloud_builder is None:
+            from .cloud import PointCloudBuilder
+
+            self._cloud_builder = PointCloudBuilder(self.streams, self.device)
+        b = self._buf
+        return self._cloud_builder.build(b["disp"], b["Q"], color=self._last_rect_left, bgr=True, z_range=z_range,
+                                         stride=stride, organized=organized)
 
 
 # ---------------------------------------------------------------------- one rig
@@ -372,3 +389,8 @@ class ClassicDepth:
 
     def _readout(self) -> float:
         return float(self._batch._readout()[0])
+
+    def cloud(self, z_range=(-float("inf"), float("inf")), stride: int = 1, organized: bool = False):
+        """The coloured point cloud of the last step: ClassicDepthBatch.cloud with one stream (a cloud.CloudResult whose
+        stream 0 is this rig: ``.numpy(0)``, ``.save_ply([path])``)."""
+        return self._batch.cloud(z_range=z_range, stride=stride, organized=organized)
