@@ -233,6 +233,9 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_cloud_ws_bytes": (ctypes.c_longlong, [_i, _i, _i, _i]),
     "sd_cloud_build_n": (_i, [_i, _p, _p, _i, _i, _i, _p, _f, _f, _i, _p, _p, ctypes.c_longlong, _p, _p, _p]),
     "sd_write_ply_batch": (_i, [_p, _i, _p, ctypes.c_longlong, _p, _i, ctypes.c_char_p, _i]),
+    # the label-free check: visibility classes and photometric residual
+    "sd_stereo_check_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
+    "sd_stereo_check": (_i, [_i, _p, _p, _p, _i, _i, _f, _f, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -5,7 +5,8 @@
         [--height H --width W] [--precision fp32|bf16|fp8] [--base-channels 32] [--batch-size 32] [--max-samples 0] \\
         [--write-sigma] [--png-level 1] [--read-threads 16] [--device cuda] \\
         [--write-ply (--calibration FILE.npz | --focal-px F --baseline-m B [--cx X --cy Y]) \\
-         [--ply-stride 1] [--ply-min-depth M] [--ply-max-depth M]]
+         [--ply-stride 1] [--ply-min-depth M] [--ply-max-depth M]] \\
+        [--self-check [--check-occ-tol 0.5] [--check-photo-thr T] [--write-check] [--ply-visible-only]]
 
 Runs a trained checkpoint (``cli.save_checkpoint``'s format, or the reference's) over frames on disk and
 
@@ -30,6 +31,15 @@ resolution (``sd_cloud_build_n`` on sd_disp_export's upsampled disparity and the
 counts riding the same copy back and the same writer thread. The geometry is a calibration file (keys ``Q`` and
 ``image_size``; ``cloud.rescale_Q`` for frames of another size) or an ideal rig in pixels of the frames.
 
+``--self-check`` adds the label-free check (``sd_stereo_check`` on sd_disp_export's upsampled disparity and the two
+source frames at the frame's own resolution; check.py): ``predict_meta.json`` gains a ``check`` object (the
+pixel-weighted totals over all samples, added in fp64 on the host) and ``metrics.jsonl`` the per-sample keys of
+``check.SUMMARY_KEYS``; that file is then written for a pair of directories too, holding only those keys. The frames are
+taken as rectified: FoundationStereo's are, for a pair of directories that is the user's statement. ``--write-check``
+writes ``<name>.check.png``, the picture of the check; ``--ply-visible-only`` builds the cloud from the visible pixels
+alone (``disp_vis``), which removes the occluded and out-of-view "flying" points. Without ``--self-check`` every output
+is byte for byte what it is without these flags.
+
 ``--precision fp8``: the first batch is the calibration forward (its activations set the static e4m3 scales of all
 later batches), and the scales are per tensor over the batch, as in ``LiveDepthBatch``; there are no per-sample scales.
 ``--device cpu`` is rejected (no CPU path).
@@ -50,6 +60,10 @@ import torch
 
 from . import _lib as L
 from .cache import plan_batches
+from .check import ROW as CHECK_ROW
+from .check import CheckOptions, check_options
+from .check import aggregate_rows as aggregate_check_rows
+from .check import summary_from_row as check_summary_from_row
 from .dataset import (discover_samples, read_png_batch, read_rgb_uint8, sample_cache_relpath, write_png_batch)
 
 IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg")
@@ -151,6 +165,19 @@ def ply_relpath(relpath: Path) -> Path:
     return relpath.with_suffix(".ply")
 
 
+def check_relpath(relpath: Path) -> Path:
+    return relpath.with_suffix(".check.png")
+
+
+CHECK_KEYWORDS = ("self_check", "check_occ_tol", "check_photo_thr", "write_check", "ply_visible_only")
+
+
+def _split_check(kw: dict) -> tuple[dict, dict]:
+    """The keywords of ``cloud_options`` and those of ``check_options`` out of one ``**`` dict."""
+    return ({k: v for k, v in kw.items() if k not in CHECK_KEYWORDS},
+            {k: v for k, v in kw.items() if k in CHECK_KEYWORDS})
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Predict disparity files from stereo pairs on disk and evaluate them.")
     p.add_argument("--checkpoint", type=str, required=True, help="Checkpoint of the training CLI (or the reference's).")
@@ -178,6 +205,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ply-stride", type=int, default=1, help="Keep every n-th pixel in x and y, 1..64.")
     p.add_argument("--ply-min-depth", type=float, default=None, help="Smallest kept Z in metres (default: no bound).")
     p.add_argument("--ply-max-depth", type=float, default=None, help="Largest kept Z in metres (default: no bound).")
+    p.add_argument("--self-check", action="store_true",
+                   help="Label-free check of every sample: visibility classes and photometric residual (frames rectified).")
+    p.add_argument("--check-occ-tol", type=float, default=None, help="Occlusion tolerance in pixels (default 0.5).")
+    p.add_argument("--check-photo-thr", type=float, default=None,
+                   help="Residual (codes summed over the channels, 0..765) above which a visible pixel is a mismatch.")
+    p.add_argument("--write-check", action="store_true", help="Also write <name>.check.png (needs --output-root).")
+    p.add_argument("--ply-visible-only", action="store_true", help="Clouds from the visible pixels only (needs --write-ply).")
     return p
 
 
@@ -251,6 +285,7 @@ class Predictor:
         self._calibrated = False
         self._buf: dict = {}
         self._cloud_buf: dict = {}
+        self._check_buf: dict = {}
 
     def _buffers(self, n: int, Hs: int, Ws: int, sigma: bool) -> dict:
         """Device buffers for batches of up to n samples of one source size (grown, never shrunk)."""
@@ -296,15 +331,38 @@ class Predictor:
             self._cloud_buf[key] = b
         return b
 
+    def _check_buffers(self, n: int, Hs: int, Ws: int, check: CheckOptions, own_disp: bool) -> dict:
+        """Device buffers of the check stage for batches of up to n samples of one source size (grown, never shrunk).
+        own_disp: no cloud stage holds the upsampled disparity, so this one does."""
+        key = (Hs, Ws, check.write_check, check.ply_visible_only)
+        b = self._check_buf.get(key)
+        if b is None or b["n"] < n or (own_disp and b["disp_up"] is None):
+            dev = self.device
+            nb = max(n, b["n"]) if b is not None else n
+            with torch.inference_mode(False):
+                b = {"n": nb,
+                     "disp_up": torch.empty(nb, Hs, Ws, device=dev) if own_disp else None,
+                     "rows": torch.empty(nb, CHECK_ROW, device=dev, dtype=torch.float64),
+                     "vis_rgb": torch.empty(nb, Hs, Ws, 3, device=dev, dtype=torch.uint8) if check.write_check else None,
+                     "disp_vis": torch.empty(nb, Hs, Ws, device=dev) if check.ply_visible_only else None,
+                     "work": torch.empty(L.call("sd_stereo_check_ws_bytes", nb, Hs, Ws) // 8, device=dev,
+                                         dtype=torch.float64)}
+            self._check_buf[key] = b
+        return b
+
     def run(self, left_u8: torch.Tensor, right_u8: torch.Tensor, gt_rgb: torch.Tensor | None = None,
-            sigma: bool = False, images: bool = True, cloud: CloudOptions | None = None) -> dict:
+            sigma: bool = False, images: bool = True, cloud: CloudOptions | None = None,
+            check: CheckOptions | None = None) -> dict:
         """left_u8, right_u8 (and gt_rgb, the RGB24 ground truth): contiguous uint8 [n,Hs,Ws,3] on the model's device.
         Queues the batch on the current stream and returns device tensors without synchronising: ``disp_rgb`` and
         ``sigma_rgb`` uint8 [n,Hs,Ws,3] (None unless asked for), ``rows`` float64 [n,8] (None without gt_rgb). They are
         views of buffers the next ``run`` at this source size overwrites. With ``cloud`` the result also holds
         ``disp_up`` float32 [n,Hs,Ws] (sd_disp_export's), ``points`` uint8 [n,cap,16] and ``counts`` int32 [n] (the
         bits of uint32): sd_cloud_build_n on disp_up and the left frame (RGB) at the frame's own resolution, cap the
-        lattice size."""
+        lattice size. With ``check`` it holds ``disp_up`` and ``check_rows`` float64 [n,8], ``check_rgb`` uint8
+        [n,Hs,Ws,3] with ``check.write_check`` and ``disp_vis`` float32 [n,Hs,Ws] with ``check.ply_visible_only``:
+        sd_stereo_check on disp_up and the two source frames, ahead of the cloud stage, which then builds from
+        ``disp_vis`` in place of ``disp_up``."""
         n, Hs, Ws = (int(v) for v in left_u8.shape[:3])
         for name, t in (("left_u8", left_u8), ("right_u8", right_u8), ("gt_rgb", gt_rgb)):
             if t is None:
@@ -313,11 +371,13 @@ class Predictor:
                     or t.device != self.device):
                 raise ValueError(f"Predictor.run: {name} must be a contiguous uint8 tensor of {(n, Hs, Ws, 3)} on "
                                  f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        if not (images or gt_rgb is not None or cloud is not None):
+        if not (images or gt_rgb is not None or cloud is not None or check is not None):
             raise ValueError("Predictor.run: neither images nor metrics requested")
         sigma = bool(sigma and images)
         b = self._buffers(n, Hs, Ws, sigma)
         cb = self._cloud_buffers(n, Hs, Ws, cloud) if cloud is not None else None
+        kb = self._check_buffers(n, Hs, Ws, check, cb is None) if check is not None else None
+        disp_up = cb["disp_up"] if cb is not None else (kb["disp_up"] if kb is not None else None)
         H, W = self.H, self.W
         with torch.cuda.device(self.device):
             s = L.stream_handle(self.device)
@@ -335,12 +395,17 @@ class Predictor:
             L.call("sd_disp_export", disp.data_ptr(), logvar.data_ptr() if sigma else None, n, H, W,
                    gt_rgb.data_ptr() if gt_rgb is not None else None, Hs, Ws,
                    b["disp_rgb"].data_ptr() if images else None, b["sigma_rgb"].data_ptr() if sigma else None,
-                   cb["disp_up"].data_ptr() if cb is not None else None,
+                   disp_up.data_ptr() if disp_up is not None else None,
                    b["rows"].data_ptr() if gt_rgb is not None else None, b["work"].data_ptr(), s)
+            if kb is not None:
+                L.call("sd_stereo_check", n, disp_up.data_ptr(), left_u8.data_ptr(), right_u8.data_ptr(), Hs, Ws,
+                       check.occ_tol, check.photo_thr, None, None, L.ptr(kb["disp_vis"]), L.ptr(kb["vis_rgb"]),
+                       kb["rows"].data_ptr(), kb["work"].data_ptr(), s)
             if cb is not None:
                 px, cap = Hs * Ws, cb["cap"]
+                src = kb["disp_vis"] if kb is not None and check.ply_visible_only else disp_up
                 for c0 in range(0, n, cb["streams"]):
-                    L.call("sd_cloud_build_n", min(cb["streams"], n - c0), cb["disp_up"].data_ptr() + c0 * px * 4,
+                    L.call("sd_cloud_build_n", min(cb["streams"], n - c0), src.data_ptr() + c0 * px * 4,
                            left_u8.data_ptr() + c0 * px * 3, 0, Hs, Ws, cb["Q"].data_ptr(), cloud.z_range[0],
                            cloud.z_range[1], cloud.stride, None, cb["points"].data_ptr() + c0 * cap * 16, cap,
                            cb["counts"].data_ptr() + c0 * 4, cb["work"].data_ptr(), s)
@@ -348,6 +413,10 @@ class Predictor:
                "rows": b["rows"][:n] if gt_rgb is not None else None}
         if cb is not None:
             res.update(disp_up=cb["disp_up"][:n], points=cb["points"][:n], counts=cb["counts"][:n])
+        if kb is not None:
+            res.update(disp_up=disp_up[:n], check_rows=kb["rows"][:n],
+                       check_rgb=kb["vis_rgb"][:n] if kb["vis_rgb"] is not None else None,
+                       disp_vis=kb["disp_vis"][:n] if kb["disp_vis"] is not None else None)
         return res
 
 
@@ -359,9 +428,13 @@ class PredictPipeline:
     device buffers are made once per source size (and slot) and reused by every later batch of that size."""
 
     def __init__(self, predictor: Predictor, batch_size: int, has_gt: bool, images: bool, sigma: bool,
-                 png_level: int = 1, read_threads: int = 16, cloud: CloudOptions | None = None):
+                 png_level: int = 1, read_threads: int = 16, cloud: CloudOptions | None = None,
+                 check: CheckOptions | None = None):
         self.p, self.bmax, self.has_gt, self.images, self.sigma = predictor, batch_size, has_gt, images, sigma and images
         self.cloud = cloud
+        self.check = check
+        self._chk = [{}, {}]  # per slot: source size -> (check rows [bmax,8], picture [bmax,Hs,Ws,3] or None) pinned
+        self.check_rows: list = []  # with check: the rows (float64 [n,8]) of every written batch, in order
         self._ply = [{}, {}]  # per slot: source size -> (records [bmax,cap,16], counts [bmax]) pinned
         self.point_counts: list = []  # with cloud: the counts (uint32 [n]) of every written batch, in order
         self.level, self.threads = png_level, read_threads
@@ -396,6 +469,13 @@ class PredictPipeline:
                                    torch.zeros(self.bmax, dtype=torch.int32).pin_memory())
         return self._ply[slot][hw]
 
+    def _pinned_check(self, slot: int, hw):
+        if hw not in self._chk[slot]:
+            self._chk[slot][hw] = (torch.zeros(self.bmax, CHECK_ROW, dtype=torch.float64).pin_memory(),
+                                   torch.empty(self.bmax, *hw, 3, dtype=torch.uint8).pin_memory()
+                                   if self.check.write_check else None)
+        return self._chk[slot][hw]
+
     def decode(self, slot: int, hw, items) -> list[tuple]:
         """Source frames of one batch as parts (left, right[, ground truth]), each uint8 [n,Hs,Ws,3] pinned and of one
         source size, in the batch's order."""
@@ -421,7 +501,8 @@ class PredictPipeline:
 
     def device_work(self, slot: int, parts):
         """Queues one batch on the side stream. Returns (event, [(n, (Hs, Ws), pinned disp_rgb, sigma_rgb, rows,
-        records, counts)]); the last two are None without a cloud."""
+        records, counts, check rows, check picture)]); records and counts are None without a cloud, the last two
+        without a check (the picture also without ``write_check``)."""
         dev, outs = self.device, []
         with torch.cuda.stream(self.stream):
             off: dict = {}
@@ -435,7 +516,7 @@ class PredictPipeline:
                 for d, h in zip(up, part):
                     d.copy_(h, non_blocking=True)
                 res = self.p.run(up[0], up[1], up[2] if self.has_gt else None, sigma=self.sigma, images=self.images,
-                                 cloud=self.cloud)
+                                 cloud=self.cloud, check=self.check)
                 o = off.get(hw, 0)  # parts of one size within a batch share the slot's buffers
                 off[hw] = o + n
                 h_disp, h_sigma, h_rows = self._pinned_out(slot, hw)
@@ -452,20 +533,31 @@ class PredictPipeline:
                     h_pts, h_cnt = (t[o:o + n] for t in self._pinned_ply(slot, hw))
                     h_pts.copy_(res["points"], non_blocking=True)
                     h_cnt.copy_(res["counts"], non_blocking=True)
+                h_crow = h_cvis = None
+                if self.check is not None:  # the rows (and the picture) ride the same copy-back
+                    h_crow, h_cvis = (t[o:o + n] if t is not None else None for t in self._pinned_check(slot, hw))
+                    h_crow.copy_(res["check_rows"], non_blocking=True)
+                    if h_cvis is not None:
+                        h_cvis.copy_(res["check_rgb"], non_blocking=True)
                 outs.append((n, hw, h_disp[o:o + n] if self.images else None,
-                             h_sigma[o:o + n] if self.sigma else None, h_rows[o:o + n], h_pts, h_cnt))
+                             h_sigma[o:o + n] if self.sigma else None, h_rows[o:o + n], h_pts, h_cnt, h_crow, h_cvis))
             ev = torch.cuda.Event()
             ev.record(self.stream)
         return ev, outs
 
-    def write(self, paths, sigma_paths, ev: torch.cuda.Event, outs, ply_paths=None) -> np.ndarray:
+    def write(self, paths, sigma_paths, ev: torch.cuda.Event, outs, ply_paths=None, check_paths=None) -> np.ndarray:
         """Waits for the batch, writes its files (paths: one per sample in batch order, or None) and returns its rows.
-        With a cloud, the batch's point counts are appended to ``point_counts``."""
+        With a cloud, the batch's point counts are appended to ``point_counts``; with a check, its rows to
+        ``check_rows``."""
         from .cloud import write_ply_batch
 
         ev.synchronize()
         k, rows = 0, []
-        for n, hw, h_disp, h_sigma, h_rows, h_pts, h_cnt in outs:
+        for n, hw, h_disp, h_sigma, h_rows, h_pts, h_cnt, h_crow, h_cvis in outs:
+            if h_crow is not None:
+                self.check_rows.append(h_crow.numpy().copy())
+                if check_paths is not None and h_cvis is not None:
+                    write_png_batch(check_paths[k:k + n], hw, h_cvis, self.level, self.threads)
             if h_pts is not None:
                 counts = h_cnt.numpy().view(np.uint32).copy()
                 if ply_paths is not None:
@@ -493,6 +585,7 @@ def load_model(checkpoint, precision: str = "fp32", base_channels: int = 32, dev
 def _run(items: list[PredictItem], mode: str, source: str, described: dict, checkpoint, model, output_root, height,
          width, precision, base_channels, batch_size, max_samples, write_sigma, png_level, read_threads, device,
          ply: dict | None = None) -> dict:
+    ply, chk = _split_check(ply or {})
     dev = _resolve_device(device)
     if batch_size < 1:
         raise ValueError(f"--batch-size must be >= 1, got: {batch_size}")
@@ -503,7 +596,8 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
         raise ValueError("Nothing to do: no ground truth to evaluate against and no --output-root to write to.")
     if write_sigma and output_root is None:
         raise ValueError("--write-sigma needs --output-root.")
-    cloud = cloud_options(output_root=output_root, **(ply or {}))
+    cloud = cloud_options(output_root=output_root, **ply)
+    check = check_options(output_root=output_root, write_ply=cloud is not None, **chk)
     if max_samples > 0:
         items = items[:max_samples]
     if not items:
@@ -531,7 +625,7 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
     batches = plan_batches(items, batch_size)
     predictor = Predictor(model, (width, height))
     pipe = PredictPipeline(predictor, batch_size, has_gt, out_root is not None, write_sigma, png_level, read_threads,
-                           cloud)
+                           cloud, check)
     events, writes, held = [None, None], [None, None], [None, None]
     done: list = []  # (batch's items, future of its rows) in order
     try:
@@ -551,7 +645,9 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
                 paths = [out_root / it.relpath for it in its] if out_root is not None else None
                 spaths = [out_root / sigma_relpath(it.relpath) for it in its] if (out_root and write_sigma) else None
                 ppaths = [out_root / ply_relpath(it.relpath) for it in its] if (out_root and cloud) else None
-                writes[k] = writer.submit(pipe.write, paths, spaths, events[k], outs, ppaths)
+                cpaths = [out_root / check_relpath(it.relpath) for it in its] \
+                    if (out_root and check and check.write_check) else None
+                writes[k] = writer.submit(pipe.write, paths, spaths, events[k], outs, ppaths, cpaths)
                 done.append((its, writes[k]))
             rows = [(its, w.result()) for its, w in done]
     finally:
@@ -583,19 +679,25 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
     if cloud is not None:  # one .ply per sample beside its disparity file (not counted in num_written)
         points = np.concatenate(pipe.point_counts).astype(np.int64)
         meta.update(cloud.describe(), points=int(points.sum()))
+    crows = None
+    if check is not None:  # one .check.png per sample with write_check (not counted in num_written)
+        crows = np.concatenate(pipe.check_rows)
+        meta.update(check.describe(), check=aggregate_check_rows(crows))
     if has_gt:
         all_rows = np.concatenate([r for _, r in rows])
         meta.update(aggregate_rows(all_rows))
-        if out_root is not None:
-            with open(out_root / "metrics.jsonl", "w", encoding="utf-8") as f:
-                k = 0
-                for (its, r) in rows:
-                    for it, row in zip(its, r):
-                        rec = {"sample": it.relpath.as_posix(), **metrics_from_row(row)}
-                        if points is not None:
-                            rec["points"] = int(points[k])
-                        f.write(json.dumps(rec) + "\n")
-                        k += 1
+    if (has_gt or check is not None) and out_root is not None:  # without ground truth: the check's keys alone
+        with open(out_root / "metrics.jsonl", "w", encoding="utf-8") as f:
+            k = 0
+            for (its, r) in rows:
+                for it, row in zip(its, r):
+                    rec = {"sample": it.relpath.as_posix(), **(metrics_from_row(row) if has_gt else {})}
+                    if points is not None and has_gt:
+                        rec["points"] = int(points[k])
+                    if crows is not None:
+                        rec.update(check_summary_from_row(crows[k]))
+                    f.write(json.dumps(rec) + "\n")
+                    k += 1
     if out_root is not None:
         (out_root / "predict_meta.json").write_text(json.dumps(meta, indent=2), encoding="utf-8")
     print(json.dumps(meta))
@@ -610,7 +712,9 @@ def predict_dataset(checkpoint, dataset_root, output_root=None, *, model=None, h
     Returns the dict that is also written to ``predict_meta.json`` and printed as one JSON line. ``ply``: the keywords
     of ``cloud_options`` (write_ply=True, then calibration=FILE or focal_px= and baseline_m=, optionally cx=, cy=,
     ply_stride=, ply_min_depth=, ply_max_depth=): also ``<scene>/<frame>.ply``, the coloured point cloud of each sample
-    at the frame's own resolution."""
+    at the frame's own resolution. It also takes the keywords of ``check.check_options`` (self_check=True, then
+    optionally check_occ_tol=, check_photo_thr=, write_check=, ply_visible_only=): the label-free check of every sample,
+    its totals under ``check`` in the returned dict and its per-sample keys in ``metrics.jsonl``."""
     _resolve_device(device)
     root = Path(dataset_root).expanduser().resolve()
     items = dataset_items(root)
@@ -623,7 +727,8 @@ def predict_pairs(checkpoint, left_dir, right_dir, output_root, *, model=None, h
                   precision: str = "fp32", base_channels: int = 32, batch_size: int = 32, max_samples: int = 0,
                   write_sigma: bool = False, png_level: int = 1, read_threads: int = 16, device="cuda", **ply) -> dict:
     """Two directories of frames paired by stem: ``<output_root>/<stem>.png`` (and ``<stem>.ply`` with the ``ply``
-    keywords of ``predict_dataset``), no metrics."""
+    keywords of ``predict_dataset``), no metrics against ground truth. With ``self_check=True`` (and the other keywords
+    of ``check.check_options``) ``metrics.jsonl`` is written with the check's per-sample keys alone."""
     _resolve_device(device)
     if output_root is None:
         raise ValueError("Nothing to do: no ground truth to evaluate against and no --output-root to write to.")
@@ -649,6 +754,10 @@ def main(argv=None) -> dict:
         common.update(write_ply=a.write_ply, calibration=a.calibration, focal_px=a.focal_px, baseline_m=a.baseline_m,
                       cx=a.cx, cy=a.cy, ply_stride=a.ply_stride, ply_min_depth=a.ply_min_depth,
                       ply_max_depth=a.ply_max_depth)
+    if a.self_check or a.write_check or a.ply_visible_only or a.check_occ_tol is not None \
+            or a.check_photo_thr is not None:
+        common.update(self_check=a.self_check, check_occ_tol=a.check_occ_tol, check_photo_thr=a.check_photo_thr,
+                      write_check=a.write_check, ply_visible_only=a.ply_visible_only)
     if a.dataset_root is not None:
         return predict_dataset(a.checkpoint, a.dataset_root, a.output_root, **common)
     return predict_pairs(a.checkpoint, a.left_dir, a.right_dir, a.output_root, **common)

@@ -242,7 +242,9 @@ class ClassicDepthBatch:
         self._buf = None
         self._key = None
         self._last_rect_left = None  # the last step's rectified left frames: the colours of cloud()
+        self._last_rect_right = None  # with rect_left: the frames of check()
         self._cloud_builder = None
+        self._checker = None
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, H: int, W: int):
@@ -332,7 +334,7 @@ class ClassicDepthBatch:
             L.call("sd_sgm_center_n", n, b["z"].data_ptr(), H, W, self.center_window, b["center"].data_ptr(), s)
             L.call("sd_live_compose_n", n, b["code"].data_ptr(), b["lut"].data_ptr(), b["vis"].data_ptr(), None, None,
                    None, None, None, None, H, W, H, W, 0, s)
-        self._last_rect_left = rect_l
+        self._last_rect_left, self._last_rect_right = rect_l, rect_r
         return ClassicResult(self, disparity_q4=b["q"], disparity=b["disp"], depth_m=b["z"], rect_left=rect_l,
                              rect_right=rect_r, disp_vis=b["vis"])
 
@@ -357,6 +359,19 @@ class ClassicDepthBatch:
         b = self._buf
         return self._cloud_builder.build(b["disp"], b["Q"], color=self._last_rect_left, bgr=True, z_range=z_range,
                                          stride=stride, organized=organized)
+
+    def check(self, occ_tol: float = 0.5, photo_thr: float = float("inf")):
+        """The label-free check of the last step (check.StereoCheck.run on its disparity, rect_left and rect_right; the
+        NaN holes of the disparity are class 1): a check.CheckResult of n streams. Launches only; the checker and its
+        buffers are made at the first call. step() itself runs nothing of this."""
+        if self._buf is None or self._last_rect_left is None:
+            raise RuntimeError("check() before the first step")
+        if self._checker is None:
+            from .check import StereoCheck
+
+            self._checker = StereoCheck(self.streams, self.device)
+        return self._checker.run(self._buf["disp"], self._last_rect_left, self._last_rect_right, occ_tol=occ_tol,
+                                 photo_thr=photo_thr)
 
 
 # ---------------------------------------------------------------------- one rig
@@ -394,3 +409,8 @@ class ClassicDepth:
         """The coloured point cloud of the last step: ClassicDepthBatch.cloud with one stream (a cloud.CloudResult whose
         stream 0 is this rig: ``.numpy(0)``, ``.save_ply([path])``)."""
         return self._batch.cloud(z_range=z_range, stride=stride, organized=organized)
+
+    def check(self, occ_tol: float = 0.5, photo_thr: float = float("inf")):
+        """The label-free check of the last step: ClassicDepthBatch.check with one stream (a check.CheckResult whose
+        sample 0 is this rig)."""
+        return self._batch.check(occ_tol=occ_tol, photo_thr=photo_thr)
