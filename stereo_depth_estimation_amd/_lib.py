@@ -236,6 +236,9 @@ PROTOTYPES: dict[str, tuple] = {
     # the label-free check: visibility classes and photometric residual
     "sd_stereo_check_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
     "sd_stereo_check": (_i, [_i, _p, _p, _p, _i, _i, _f, _f, _p, _p, _p, _p, _p, _p, _p]),
+    # label-free adaptation: photometric + smoothness loss and its gradient for the heads' GRADS mode
+    "sd_selfsup_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
+    "sd_selfsup_loss": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None
