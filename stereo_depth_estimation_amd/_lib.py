@@ -308,6 +308,18 @@ def stream_handle(device=None) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def grow(owner, name: str, numel: int, dtype) -> torch.Tensor:
+    """The flat buffer `owner.<name>` on `owner.device`, at least `numel` elements: kept while it is large enough, else
+    released and made anew (an ordinary tensor, also under inference_mode)."""
+    t = getattr(owner, name)
+    if t is None or t.numel() < numel or t.device != owner.device:
+        setattr(owner, name, None)  # released before the larger one is made
+        with torch.inference_mode(False):
+            t = torch.empty(numel, dtype=dtype, device=owner.device)
+        setattr(owner, name, t)
+    return t
+
+
 def make_src(
     src0,
     c0: int,

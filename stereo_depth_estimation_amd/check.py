@@ -148,15 +148,6 @@ class StereoCheck:
             raise RuntimeError(f"StereoCheck runs only on a HIP device (no CPU path), got {device}")
         self._cls = self._resid = self._disp_vis = self._vis_rgb = self._rows = self._work = self._pin = None
 
-    def _grow(self, name: str, numel: int, dtype) -> torch.Tensor:
-        t = getattr(self, name)
-        if t is None or t.numel() < numel or t.device != self.device:
-            setattr(self, name, None)  # released before the larger one is made
-            with torch.inference_mode(False):
-                t = torch.empty(numel, dtype=dtype, device=self.device)
-            setattr(self, name, t)
-        return t
-
     def run(self, disp: torch.Tensor, left: torch.Tensor | None = None, right: torch.Tensor | None = None,
             occ_tol: float = 0.5, photo_thr: float = math.inf, want=None) -> CheckResult:
         """disp: float32 [n, H, W] on the device (n <= streams), the left view's disparity in pixels of these frames,
@@ -196,14 +187,14 @@ class StereoCheck:
         left, right = (left.contiguous(), right.contiguous()) if frames else (None, None)
         px = n * H * W
         with torch.cuda.device(self.device):
-            cls = self._grow("_cls", px, torch.uint8)[:px].view(n, H, W) if "cls" in want else None
-            resid = self._grow("_resid", px, torch.float32)[:px].view(n, H, W) if "resid" in want else None
-            dvis = self._grow("_disp_vis", px, torch.float32)[:px].view(n, H, W) if "disp_vis" in want else None
-            vis = self._grow("_vis_rgb", px * 3, torch.uint8)[:px * 3].view(n, H, W, 3) if "vis_rgb" in want else None
+            cls = L.grow(self, "_cls", px, torch.uint8)[:px].view(n, H, W) if "cls" in want else None
+            resid = L.grow(self, "_resid", px, torch.float32)[:px].view(n, H, W) if "resid" in want else None
+            dvis = L.grow(self, "_disp_vis", px, torch.float32)[:px].view(n, H, W) if "disp_vis" in want else None
+            vis = L.grow(self, "_vis_rgb", px * 3, torch.uint8)[:px * 3].view(n, H, W, 3) if "vis_rgb" in want else None
             rows = work = None
             if "rows" in want:
-                rows = self._grow("_rows", self.streams * ROW, torch.float64)[:n * ROW].view(n, ROW)
-                work = self._grow("_work", L.call("sd_stereo_check_ws_bytes", n, H, W) // 8, torch.float64)
+                rows = L.grow(self, "_rows", self.streams * ROW, torch.float64)[:n * ROW].view(n, ROW)
+                work = L.grow(self, "_work", L.call("sd_stereo_check_ws_bytes", n, H, W) // 8, torch.float64)
                 if self._pin is None:
                     self._pin = torch.zeros(self.streams, ROW, dtype=torch.float64).pin_memory()
             L.call("sd_stereo_check", n, disp.data_ptr(), L.ptr(left), L.ptr(right), H, W, tol, thr, L.ptr(cls),

@@ -200,15 +200,6 @@ class PointCloudBuilder:
         self._points = self._xyz = self._work = self._count = self._pin = self._Qdev = None
         self._Qhost = None
 
-    def _grow(self, name: str, numel: int, dtype) -> torch.Tensor:
-        t = getattr(self, name)
-        if t is None or t.numel() < numel or t.device != self.device:
-            setattr(self, name, None)  # released before the larger one is made
-            with torch.inference_mode(False):
-                t = torch.empty(numel, dtype=dtype, device=self.device)
-            setattr(self, name, t)
-        return t
-
     def _matrices(self, Q, n: int) -> torch.Tensor:
         """Qdev f64 [n, 16]. A float64 device tensor [n, 16] / [n, 4, 4] is taken as it is (the caller checked it); host
         matrices are checked and uploaded when they differ from the last call's."""
@@ -259,11 +250,11 @@ class PointCloudBuilder:
         color = color.contiguous() if color is not None else None
         with torch.cuda.device(self.device):
             Qdev = self._matrices(Q, n)
-            points = self._grow("_points", n * cap * 16, torch.uint8)[:n * cap * 16].view(n, cap, 16)
-            xyz = self._grow("_xyz", n * H * W * 3, torch.float32)[:n * H * W * 3].view(n, H, W, 3) if organized \
+            points = L.grow(self, "_points", n * cap * 16, torch.uint8)[:n * cap * 16].view(n, cap, 16)
+            xyz = L.grow(self, "_xyz", n * H * W * 3, torch.float32)[:n * H * W * 3].view(n, H, W, 3) if organized \
                 else None
-            work = self._grow("_work", L.call("sd_cloud_ws_bytes", n, H, W, stride) // 4, torch.int32)
-            count = self._grow("_count", self.streams, torch.int32)[:n]
+            work = L.grow(self, "_work", L.call("sd_cloud_ws_bytes", n, H, W, stride) // 4, torch.int32)
+            count = L.grow(self, "_count", self.streams, torch.int32)[:n]
             if self._pin is None:
                 self._pin = torch.zeros(MAX_STREAMS, dtype=torch.int32).pin_memory()
             L.call("sd_cloud_build_n", n, disparity.data_ptr(), L.ptr(color), int(bool(bgr)), H, W, Qdev.data_ptr(),

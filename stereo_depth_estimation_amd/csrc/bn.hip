@@ -5,6 +5,7 @@
 // epilogue (conv_gemm.hip); finalize reduces them in fp64 (ATen CPU accumulates BN moments in
 // double) and emits the fused affine (scale, shift) consumed by the next GEMM's gather.
 #include "common.h"
+#include "stage_util.h"
 
 namespace {
 
@@ -336,11 +337,7 @@ __global__ __launch_bounds__(256) void k_pool_bwd_add(const T* __restrict__ y, c
     }
 }
 
-int grid_for(long long work) {
-    long long g = (work + 255) / 256;
-    if (g > 8192) g = 8192;
-    return (int)(g < 1 ? 1 : g);
-}
+int grid_for(long long work) { return grid_for(work, 8192); }  // stage_util.h
 
 // Blocks of 256 threads of `kernel` resident on the whole device at once (occupancy x CUs), or
 // `fallback` when the runtime cannot say. Grid-stride kernels launched with more blocks than this run a

@@ -23,35 +23,16 @@
 #include <math.h>
 
 #include "common.h"
+#include "stage_util.h"
 
 // the restatement rounds every operation on its own: nothing here may fuse (r_c = a + f (b - a) is two roundings)
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int CHECK_THREADS = 256;  // four waves
-constexpr int CHECK_PX = 4;         // consecutive pixels per thread
-constexpr int CHECK_SCAN = CHECK_THREADS * CHECK_PX;  // pixels per step of the row walk (check.SCAN_PIXELS)
-constexpr int CHECK_MAX_BLOCKS = 1024;                // partial rows per sample at most
-constexpr int CHECK_SMALL_ROWS = 16;                  // rows a block owns at most because W is small
-constexpr int CHECK_ROW = 8;
-constexpr int CHECK_SUM_THREADS = 512;  // of the launch that adds the partial rows: 64 partial rows x 8 columns a step
-
-bool check_sizes_ok(int n, int H, int W) {
-    return n >= 1 && n <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 31);
-}
-// rows per block: CHECK_SCAN / W of them when W is small (16 at most), more when H exceeds what CHECK_MAX_BLOCKS
-// blocks cover. A function of (H, W) alone, as is the number of blocks (= partial rows per sample).
-int check_rows_per_block(int H, int W) {
-    int r = CHECK_SCAN / W;
-    r = r < 1 ? 1 : (r > CHECK_SMALL_ROWS ? CHECK_SMALL_ROWS : r);
-    const int need = (H + CHECK_MAX_BLOCKS - 1) / CHECK_MAX_BLOCKS;
-    return r > need ? r : need;
-}
-int check_blocks(int H, int W) {
-    const int r = check_rows_per_block(H, W);
-    return (H + r - 1) / r;
-}
+// the row walk's shape, the sizes it accepts and the blocks it takes are stage_util.h's row_walk
+constexpr int CHECK_THREADS = row_walk::THREADS, CHECK_PX = row_walk::PX, CHECK_ROW = row_walk::ROW;
+constexpr int CHECK_SCAN = row_walk::STEP;  // pixels per step of the row walk (check.SCAN_PIXELS)
 
 struct CheckArgs {
     const float* disp;
@@ -65,13 +46,6 @@ struct CheckArgs {
     int H, W, rows_per;
     float occ_tol, photo_thr;
 };
-
-__device__ __forceinline__ void check_store_rgb4(uint8_t* dst, const uint32_t (&v)[4]) {  // 12 bytes, 4-B aligned
-    uint32_t* w = reinterpret_cast<uint32_t*>(dst);
-    w[0] = v[0] | v[1] << 24;
-    w[1] = v[1] >> 8 | v[2] << 16;
-    w[2] = v[2] >> 16 | v[3] << 8;
-}
 
 // VEC: W % 4 == 0, so a thread's four pixels are all inside the row or all outside, and every pointer is aligned:
 // 16-B loads of disp, word loads of left, word and 16-B stores. Otherwise scalar loads and stores, any width and
@@ -193,7 +167,7 @@ __global__ __launch_bounds__(CHECK_THREADS) void k_stereo_check(CheckArgs a) {
                 if (a.resid) *reinterpret_cast<float4*>(a.resid + row + xb) = make_float4(rs[0], rs[1], rs[2], rs[3]);
                 if (a.disp_vis)
                     *reinterpret_cast<float4*>(a.disp_vis + row + xb) = make_float4(dv[0], dv[1], dv[2], dv[3]);
-                if (a.vis_rgb) check_store_rgb4(a.vis_rgb + (row + xb) * 3, col);
+                if (a.vis_rgb) st_rgb<4>(a.vis_rgb + (row + xb) * 3, col);
             } else {
 #pragma unroll
                 for (int p = 0; p < CHECK_PX; ++p) {
@@ -202,63 +176,21 @@ __global__ __launch_bounds__(CHECK_THREADS) void k_stereo_check(CheckArgs a) {
                     if (a.cls) a.cls[i] = (uint8_t)cl[p];
                     if (a.resid) a.resid[i] = rs[p];
                     if (a.disp_vis) a.disp_vis[i] = dv[p];
-                    if (a.vis_rgb) {
-                        uint8_t* o = a.vis_rgb + i * 3;
-                        o[0] = (uint8_t)col[p], o[1] = (uint8_t)(col[p] >> 8), o[2] = (uint8_t)(col[p] >> 16);
-                    }
+                    if (a.vis_rgb) st_rgb1(a.vis_rgb + i * 3, col[p]);
                 }
             }
         }
     }
     if (a.partial == nullptr) return;  // uniform over the grid
-    // the block's row: each wave by a shuffle tree, then the four waves in order (counts are exact as doubles)
-    double v[7] = {(double)n_val, (double)n_oov, (double)n_occ, (double)n_cnt, se, se2, (double)n_mis};
-    __shared__ double red[CHECK_THREADS / 64][CHECK_ROW];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) v[k] += __shfl_down(v[k], s);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 7; ++k) red[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (tid < CHECK_ROW) {
-        double t = 0.0;
-        if (tid < 7) t = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-        a.partial[((size_t)sid * gridDim.x + blockIdx.x) * CHECK_ROW + tid] = t;
-    }
-}
-
-// rows[b][k] = the sum of the sample's partial rows; one block per sample, thread = (partial row j of 64, column k of
-// 8). Thread (j, k) adds column k of the partial rows j, j + 64, ... in that order (independent loads: with a thousand
-// partial rows a single chain of them was most of the stage's time at n = 1), a wave adds its eight j by shuffles and
-// the eight waves are added in order: one fixed order for a given number of partial rows.
-__global__ __launch_bounds__(CHECK_SUM_THREADS) void k_stereo_check_rows(const double* __restrict__ partial, int nblk,
-                                                                         double* __restrict__ rows) {
-    const int b = blockIdx.x, k = threadIdx.x & (CHECK_ROW - 1), j = threadIdx.x >> 3;
-    const double* p = partial + (size_t)b * nblk * CHECK_ROW;
-    double t = 0.0;
-    for (int i = j; i < nblk; i += CHECK_SUM_THREADS / CHECK_ROW) t += p[(size_t)i * CHECK_ROW + k];
-#pragma unroll
-    for (int s = 32; s >= CHECK_ROW; s >>= 1) t += __shfl_down(t, s);
-    __shared__ double red[CHECK_SUM_THREADS / 64][CHECK_ROW];
-    if ((threadIdx.x & 63) < CHECK_ROW) red[threadIdx.x >> 6][k] = t;
-    __syncthreads();
-    if (threadIdx.x < CHECK_ROW) {
-        double sum = red[0][k];
-#pragma unroll
-        for (int w = 1; w < CHECK_SUM_THREADS / 64; ++w) sum += red[w][k];
-        rows[(size_t)b * CHECK_ROW + k] = sum;
-    }
+    const double v[7] = {(double)n_val, (double)n_oov, (double)n_occ, (double)n_cnt, se, se2, (double)n_mis};
+    block_partial_row<CHECK_THREADS>(v, a.partial + ((size_t)sid * gridDim.x + blockIdx.x) * CHECK_ROW);
 }
 
 }  // namespace
 
 extern "C" long long sd_stereo_check_ws_bytes(int n, int H, int W) {
-    if (!check_sizes_ok(n, H, W)) return -1;
-    return (long long)n * check_blocks(H, W) * CHECK_ROW * (long long)sizeof(double);
+    if (!row_walk::sizes_ok(n, H, W)) return -1;
+    return (long long)n * row_walk::blocks(H, W) * CHECK_ROW * (long long)sizeof(double);
 }
 
 extern "C" int sd_stereo_check(int n, const float* disp, const uint8_t* left, const uint8_t* right, int H, int W,
@@ -266,7 +198,7 @@ extern "C" int sd_stereo_check(int n, const float* disp, const uint8_t* left, co
                                uint8_t* vis_rgb, double* rows, void* work, sd_stream s) {
     SD_REQUIRE(n >= 1 && n <= 65535, "sd_stereo_check: n = %d samples (1..65535)", n);
     SD_REQUIRE(disp, "sd_stereo_check: null disp");
-    SD_REQUIRE(check_sizes_ok(n, H, W), "sd_stereo_check: bad sizes H x W = %d x %d (positive, H * W < 2^31)", H, W);
+    SD_REQUIRE(row_walk::sizes_ok(n, H, W), "sd_stereo_check: bad sizes H x W = %d x %d (positive, H * W < 2^31)", H, W);
     SD_REQUIRE((left == nullptr) == (right == nullptr), "sd_stereo_check: left and right: both or neither");
     SD_REQUIRE(resid == nullptr || left != nullptr, "sd_stereo_check: resid needs frames");
     SD_REQUIRE(vis_rgb == nullptr || left != nullptr, "sd_stereo_check: vis_rgb needs frames");
@@ -286,10 +218,10 @@ extern "C" int sd_stereo_check(int n, const float* disp, const uint8_t* left, co
     a.partial = rows ? static_cast<double*>(work) : nullptr;
     a.H = H;
     a.W = W;
-    a.rows_per = check_rows_per_block(H, W);
+    a.rows_per = row_walk::rows_per_block(H, W);
     a.occ_tol = occ_tol;
     a.photo_thr = photo_thr;
-    const int nblk = check_blocks(H, W);
+    const int nblk = row_walk::blocks(H, W);
     const bool vec = W % 4 == 0 && (uintptr_t)disp % 16 == 0 && (uintptr_t)left % 4 == 0 && (uintptr_t)cls % 4 == 0 &&
                      (uintptr_t)resid % 16 == 0 && (uintptr_t)disp_vis % 16 == 0 && (uintptr_t)vis_rgb % 4 == 0;
     hipStream_t st = to_stream(s);
@@ -298,6 +230,8 @@ extern "C" int sd_stereo_check(int n, const float* disp, const uint8_t* left, co
         hipLaunchKernelGGL(k_stereo_check<true>, grid, block, 0, st, a);
     else
         hipLaunchKernelGGL(k_stereo_check<false>, grid, block, 0, st, a);
-    if (rows) hipLaunchKernelGGL(k_stereo_check_rows, dim3(n), dim3(CHECK_SUM_THREADS), 0, st, a.partial, nblk, rows);
+    if (rows)
+        hipLaunchKernelGGL((k_rows_sum<CHECK_ROW, row_walk::SUM_THREADS>), dim3(n), dim3(row_walk::SUM_THREADS), 0, st,
+                           a.partial, nblk, rows);
     return sd_check_launch("sd_stereo_check");
 }

@@ -9,6 +9,7 @@
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "stage_util.h"
 
 namespace {
 
@@ -239,11 +240,7 @@ __global__ void k_stereo_from_cache4(const uint8_t* __restrict__ left, const uin
     }
 }
 
-int grid_for(long long work) {
-    long long g = (work + 255) / 256;
-    if (g > 16384) g = 16384;
-    return (int)(g < 1 ? 1 : g);
-}
+int grid_for(long long work) { return grid_for(work, 16384); }  // stage_util.h
 
 }  // namespace
 

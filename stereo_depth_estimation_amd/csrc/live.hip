@@ -20,6 +20,8 @@
 #include <math.h>
 
 #include "common.h"
+#include "radix_select.h"
+#include "stage_util.h"
 
 // No contraction anywhere in this file: a * b + c stays two roundings unless written fmaf. HIP's __fmul_rn / __fadd_rn
 // are plain operators that the compiler may still fuse after inlining (it did, in one instantiation of the post kernel
@@ -33,39 +35,22 @@ __device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
 __device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
 __device__ __forceinline__ float div_rn(float a, float b) { return a / b; }
 
-int live_grid(long long work) {
-    long long g = (work + 255) / 256;
-    if (g > 16384) g = 16384;
-    return (int)(g < 1 ? 1 : g);
-}
+int live_grid(long long work) { return grid_for(work, 16384); }
 
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < INFINITY; }  // false for NaN
+// the values of a map that count: the auto range and the centre medians
+struct LivePositive {
+    __device__ __forceinline__ static bool test(float v) { return finite_f(v) && v > 0.f; }
+};
 
 // V consecutive elements per thread in the plane-streaming kernels (post, contours, auto-range codes): V = 4 when the
 // element count is a multiple of 4 and the pointers are aligned (16-B float and 4-B byte-plane accesses), else V = 1.
 // The gathering kernels (front end, rectified view, compose) stay one pixel per thread: four pixels per thread with
 // 12-B BGR stores measured slower (rectify 4.7 -> 7.2 us, compose 6.1 -> 7.2 us at 640x480: a quarter of the threads,
-// each with four times the dependent gather latency).
-template <int V> __device__ __forceinline__ void ld_f(const float* p, float (&v)[V]) {
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-        v[0] = p[0];
-    }
-}
+// each with four times the dependent gather latency). ld_f and st_u8 are stage_util.h's.
 template <int V> __device__ __forceinline__ void st_f(float* p, const float (&v)[V]) {
     if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
     else p[0] = v[0];
 }
-__device__ __forceinline__ uint32_t pack4(uint8_t a, uint8_t b, uint8_t c, uint8_t d) {
-    return (uint32_t)a | (uint32_t)b << 8 | (uint32_t)c << 16 | (uint32_t)d << 24;
-}
-template <int V> __device__ __forceinline__ void st_u8(uint8_t* p, const uint8_t (&v)[V]) {
-    if constexpr (V == 4) *reinterpret_cast<uint32_t*>(p) = pack4(v[0], v[1], v[2], v[3]);
-    else p[0] = v[0];
-}
-bool aligned(const void* p, unsigned a) { return ((uintptr_t)p % a) == 0; }  // NULL counts as aligned
 
 // ------------------------------------------------------------------ front end
 // Remapped pixel (y, x) of one BGR frame, values in [0, 255]. map1 int16 [Hc][Wc][2] = integer x, y; map2 uint16
@@ -315,144 +300,21 @@ __global__ __launch_bounds__(256) void k_live_edges(const float* __restrict__ de
 }
 
 // ------------------------------------------------------------------ exact order statistics (auto range)
-// Finite positive floats order like their bit patterns (< 0x7f800000, 31 bits): a three-level radix select, 11 + 11 + 9
-// bits. Level 1 histograms the top 11 bits of every valid value; a one-block scan finds, for each of the four wanted
-// ranks, the bin that holds it and the rank within the bin; level 2 histograms the next 11 bits of the values in those
-// bins, level 3 the last 9. Targets that share a prefix share a histogram. Histograms are built in LDS per block and
-// added to the global ones (non-zero bins only). The last scan writes the results and zeroes the work buffer again.
-constexpr int SEL_H1 = 0, SEL_H2 = 2048, SEL_H3 = SEL_H2 + 4 * 2048, SEL_STATE = SEL_H3 + 4 * 512;
-constexpr int SEL_WORDS = SEL_STATE + 16;  // state: n, prefix[4], rank[4]
-
-template <int LEVEL>
-__device__ __forceinline__ void sel_hist_body(const float* __restrict__ v, int P, unsigned* __restrict__ work) {
-    constexpr int BINS = LEVEL == 3 ? 512 : 2048, NH = LEVEL == 1 ? 1 : 4;
-    __shared__ unsigned h[NH * BINS];
-    for (int i = threadIdx.x; i < NH * BINS; i += 256) h[i] = 0u;
-    unsigned pf[4] = {0u, 0u, 0u, 0u};
-    bool own[4] = {true, false, false, false};
-    if (LEVEL > 1) {
-        if (work[SEL_STATE] == 0u) return;  // no valid value (uniform)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pf[j] = work[SEL_STATE + 1 + j];
-#pragma unroll
-        for (int j = 1; j < 4; ++j) own[j] = pf[j] != pf[j - 1];
+// radix_select.h's three-level select under this rule set: the finite, > 0 values count; they order like their bit
+// patterns (< 0x7f800000, 31 bits), so the key is the pattern itself, 11 + 11 + 9 bits; the quantiles are 2 % and 98 %.
+struct LiveSelect {
+    static constexpr int LAST_BITS = 9;
+    __device__ __forceinline__ static bool member(float v) { return LivePositive::test(v); }
+    __device__ __forceinline__ static unsigned key(float v) { return __float_as_uint(v); }
+    __device__ __forceinline__ static float value(unsigned key) { return __uint_as_float(key); }
+    // numpy's `linear` percentile of the sorted valid values from the two order statistics around (n - 1) * q, in fp64
+    // (lib/_function_base_impl.py: _lerp), rounded to float32 once
+    __device__ __forceinline__ static float lerp(float a, float b, double vi) {
+        const double g = vi - floor(vi), d = (double)b - (double)a;
+        return (float)(g >= 0.5 ? (double)b - d * (1.0 - g) : (double)a + d * g);
     }
-    __syncthreads();
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < P; i += gridDim.x * 256) {
-        const float x = v[i];
-        if (!(finite_f(x) && x > 0.f)) continue;
-        const unsigned key = __float_as_uint(x);
-        if (LEVEL == 1) {
-            atomicAdd(&h[key >> 20], 1u);
-        } else {
-            const unsigned hi = LEVEL == 2 ? key >> 20 : key >> 9;
-            const unsigned lo = LEVEL == 2 ? (key >> 9) & 2047u : key & 511u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (own[j] && hi == pf[j]) atomicAdd(&h[j * BINS + lo], 1u);
-        }
-    }
-    __syncthreads();
-    unsigned* g = work + (LEVEL == 1 ? SEL_H1 : LEVEL == 2 ? SEL_H2 : SEL_H3);
-    for (int i = threadIdx.x; i < NH * BINS; i += 256)
-        if (h[i]) atomicAdd(g + i, h[i]);
-}
-// work [n][SEL_WORDS], sel [n][8]
-template <int LEVEL>
-__global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ v, int P, unsigned* __restrict__ work,
-                                                  unsigned long long hold) {
-    if (bit(hold, blockIdx.y)) return;
-    sel_hist_body<LEVEL>(v + (size_t)blockIdx.y * P, P, work + (size_t)blockIdx.y * SEL_WORDS);
-}
-
-// numpy's `linear` percentile of the sorted valid values from the two order statistics around (n - 1) * q, in fp64
-// (lib/_function_base_impl.py: _lerp), rounded to float32 once
-__device__ __forceinline__ float lerp_q(float a, float b, double vi) {
-    const double g = vi - floor(vi), d = (double)b - (double)a;
-    return (float)(g >= 0.5 ? (double)b - d * (1.0 - g) : (double)a + d * g);
-}
-
-template <int LEVEL>
-__device__ __forceinline__ void sel_scan_body(unsigned* __restrict__ work, float* __restrict__ sel) {
-    constexpr int BINS = LEVEL == 3 ? 512 : 2048, PER = BINS / 256, BITS = LEVEL == 3 ? 9 : 11;
-    unsigned* st = work + SEL_STATE;
-    __shared__ unsigned part[4][256];
-    __shared__ unsigned s_pf[4], s_rk[4], s_out[4], s_n;
-    const int t = threadIdx.x;
-    if (t < 4) {
-        s_pf[t] = LEVEL == 1 ? 0u : st[1 + t];
-        s_rk[t] = LEVEL == 1 ? 0u : st[5 + t];
-    }
-    if (t == 0) s_n = LEVEL == 1 ? 0u : st[0];
-    __syncthreads();
-    const unsigned* hist[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int src = j;
-        if (LEVEL > 1)
-            while (src > 0 && s_pf[src] == s_pf[src - 1]) --src;
-        hist[j] = LEVEL == 1 ? work + SEL_H1 : work + (LEVEL == 2 ? SEL_H2 : SEL_H3) + src * BINS;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        unsigned sum = 0u;
-        for (int i = 0; i < PER; ++i) sum += hist[j][t * PER + i];
-        part[j][t] = sum;
-    }
-    __syncthreads();
-    if (LEVEL == 1 && t == 0) {
-        unsigned n = 0u;
-        for (int c = 0; c < 256; ++c) n += part[0][c];
-        s_n = n;
-        if (n > 0u) {
-            const unsigned klo = (unsigned)floor((double)(n - 1u) * 0.02), khi = (unsigned)floor((double)(n - 1u) * 0.98);
-            s_rk[0] = klo;
-            s_rk[1] = min(klo + 1u, n - 1u);
-            s_rk[2] = khi;
-            s_rk[3] = min(khi + 1u, n - 1u);
-        }
-    }
-    __syncthreads();
-    const unsigned n = s_n;
-    if (t < 4 && n > 0u) {
-        const unsigned r = s_rk[t];
-        unsigned cum = 0u;
-        int c = 0;
-        while (c < 255 && cum + part[t][c] <= r) cum += part[t][c++];
-        int b = c * PER;
-        while (b < c * PER + PER - 1 && cum + hist[t][b] <= r) cum += hist[t][b++];
-        s_out[t] = (s_pf[t] << BITS) | (unsigned)b;
-        st[1 + t] = s_out[t];
-        st[5 + t] = r - cum;
-    }
-    if (t == 0) st[0] = n;
-    if (LEVEL == 3) {
-        __syncthreads();  // the histograms were read: zero the whole work buffer for the next call
-        for (int i = t; i < SEL_WORDS; i += 256) work[i] = 0u;
-        if (t == 0) {
-            unsigned* seln = reinterpret_cast<unsigned*>(sel);
-            seln[0] = n;
-            if (n == 0u) {
-                for (int j = 1; j < 7; ++j) sel[j] = NAN;
-            } else {
-                const float a0 = __uint_as_float(s_out[0]), a1 = __uint_as_float(s_out[1]);
-                const float b0 = __uint_as_float(s_out[2]), b1 = __uint_as_float(s_out[3]);
-                sel[1] = a0;
-                sel[2] = a1;
-                sel[3] = b0;
-                sel[4] = b1;
-                sel[5] = lerp_q(a0, a1, (double)(n - 1u) * 0.02);
-                sel[6] = lerp_q(b0, b1, (double)(n - 1u) * 0.98);
-            }
-        }
-    }
-}
-template <int LEVEL>  // one block per stream
-__global__ __launch_bounds__(256) void k_sel_scan(unsigned* __restrict__ work, float* __restrict__ sel,
-                                                  unsigned long long hold) {
-    if (bit(hold, blockIdx.x)) return;
-    sel_scan_body<LEVEL>(work + (size_t)blockIdx.x * SEL_WORDS, sel + (size_t)blockIdx.x * 8);
-}
+};
+constexpr double LIVE_Q_LO = 0.02, LIVE_Q_HI = 0.98;
 
 // the auto-range codes: lo, hi and n from sd_live_select's result, on the device; scale = max(hi - lo, 1e-6) in fp64
 template <int V>
@@ -479,63 +341,14 @@ __global__ __launch_bounds__(256) void k_live_code_auto(const float* __restrict_
 }
 
 // ------------------------------------------------------------------ centre-window medians
-// block b: the median of the finite, > 0 values of map b's centre window (bounds as depth_live_dl.py:542-548), by a
-// bitonic sort of the window in LDS (<= 63 x 63 values, padded with +inf to a power of two). Even count: the fp32 mean
-// of the two middle values (numpy's median); empty: NaN.
-__device__ __forceinline__ void live_center_body(const float* m0, const float* m1, const float* m2, int H, int W,
-                                                 int window, float* __restrict__ out) {
-    const float* src = blockIdx.x == 0 ? m0 : blockIdx.x == 1 ? m1 : m2;
-    if (!src) {
-        if (threadIdx.x == 0) out[blockIdx.x] = NAN;
-        return;
-    }
-    __shared__ float buf[4096];
-    __shared__ int s_cnt;
-    if (threadIdx.x == 0) s_cnt = 0;
-    const int cx = W / 2, cy = H / 2, half = max(1, window / 2);
-    const int y0 = max(0, cy - half), y1 = min(H, cy + half + 1), x0 = max(0, cx - half), x1 = min(W, cx + half + 1);
-    const int ww = x1 - x0, total = (y1 - y0) * ww;
-    int n2 = 64;
-    while (n2 < total) n2 <<= 1;
-    __syncthreads();
-    int mine = 0;
-    for (int i = threadIdx.x; i < n2; i += 256) {
-        float x = INFINITY;
-        if (i < total) {
-            const int r = i / ww;
-            x = src[(size_t)(y0 + r) * W + x0 + (i - r * ww)];
-            if (finite_f(x) && x > 0.f) ++mine;
-            else x = INFINITY;
-        }
-        buf[i] = x;
-    }
-    if (mine) atomicAdd(&s_cnt, mine);
-    __syncthreads();
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n2; i += 256) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const float a = buf[i], b = buf[l];
-                    if ((a > b) == ((i & k) == 0)) {
-                        buf[i] = b;
-                        buf[l] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    if (threadIdx.x == 0) {
-        const int m = s_cnt;
-        out[blockIdx.x] = m == 0 ? NAN : (m & 1) ? buf[m / 2] : div_rn(add_rn(buf[m / 2 - 1], buf[m / 2]), 2.f);
-    }
-}
-// grid (3, n): out [n][3]
+// block (b, i): stage_util.h's center_median of the finite, > 0 values of stream i's map b (bounds as
+// depth_live_dl.py:542-548); a map that is not given: NaN. grid (3, n): out [n][3]
 __global__ __launch_bounds__(256) void k_live_center(const float* m0, const float* m1, const float* m2, int H, int W,
                                                      int window, float* __restrict__ out, unsigned long long hold) {
     if (bit(hold, blockIdx.y)) return;
-    const size_t o = (size_t)blockIdx.y * H * W;
-    live_center_body(m0 + o, at(m1, o), at(m2, o), H, W, window, out + (size_t)blockIdx.y * 3);
+    const float* src = blockIdx.x == 0 ? m0 : blockIdx.x == 1 ? m1 : m2;
+    const float m = src ? center_median<LivePositive>(src + (size_t)blockIdx.y * H * W, H, W, window) : NAN;
+    if (threadIdx.x == 0) out[(size_t)blockIdx.y * 3 + blockIdx.x] = m;
 }
 
 // ------------------------------------------------------------------ compose
@@ -701,18 +514,12 @@ int live_select(const char* fn, int n, const float* values, int H, int W, unsign
     SD_REQUIRE(live_dims_ok(H, W), "%s: bad sizes %dx%d", fn, H, W);
     LIVE_MASK_REQUIRE(fn, "hold_mask", hold_mask, n);
     const int P = H * W;
-    const dim3 g(cdiv(P, 1024) < 256 ? cdiv(P, 1024) : 256, n), g1(n), b(256);
     hipStream_t st = to_stream(s);
-    hipLaunchKernelGGL(k_sel_hist<1>, g, b, 0, st, values, P, work, hold_mask);
-    hipLaunchKernelGGL(k_sel_scan<1>, g1, b, 0, st, work, sel, hold_mask);
-    hipLaunchKernelGGL(k_sel_hist<2>, g, b, 0, st, values, P, work, hold_mask);
-    hipLaunchKernelGGL(k_sel_scan<2>, g1, b, 0, st, work, sel, hold_mask);
-    hipLaunchKernelGGL(k_sel_hist<3>, g, b, 0, st, values, P, work, hold_mask);
-    hipLaunchKernelGGL(k_sel_scan<3>, g1, b, 0, st, work, sel, hold_mask);
+    select_launch<LiveSelect>(n, values, P, LIVE_Q_LO, LIVE_Q_HI, work, sel, hold_mask, st);
     if (code) {
         const bool vec = P % 4 == 0 && aligned(values, 16) && aligned(code, 4);
-        hipLaunchKernelGGL(vec ? k_live_code_auto<4> : k_live_code_auto<1>, dim3(live_grid(vec ? P / 4 : P), n), b, 0, st,
-                           values, P, sel, code, hold_mask);
+        hipLaunchKernelGGL(vec ? k_live_code_auto<4> : k_live_code_auto<1>, dim3(live_grid(vec ? P / 4 : P), n), dim3(256),
+                           0, st, values, P, sel, code, hold_mask);
     }
     return sd_check_launch(fn);
 }
@@ -801,7 +608,9 @@ extern "C" int sd_live_contours(const float* depth, int H, int W, float min_dept
     return live_contours("sd_live_contours", 1, depth, H, W, min_depth, max_depth, step, edge, 0, s);
 }
 
-extern "C" long long sd_live_select_n_ws_bytes(int n) { return streams_ok(n) ? (long long)n * SEL_WORDS * 4 : -1; }
+extern "C" long long sd_live_select_n_ws_bytes(int n) {
+    return streams_ok(n) ? (long long)n * SelectLayout<LiveSelect>::WORDS * 4 : -1;
+}
 extern "C" long long sd_live_select_ws_bytes(void) { return sd_live_select_n_ws_bytes(1); }
 
 extern "C" int sd_live_select_n(int n, const float* values, int H, int W, unsigned* work, float* sel, uint8_t* code,

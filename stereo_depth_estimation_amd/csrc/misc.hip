@@ -4,6 +4,7 @@
 #include <stdio.h>
 
 #include "common.h"
+#include "stage_util.h"
 
 static thread_local char g_err[512] = "";
 
@@ -465,11 +466,7 @@ __global__ void k_resize_bilinear(const float* __restrict__ in, int planes, int 
     }
 }
 
-int grid_for(long long work) {
-    long long g = (work + 255) / 256;
-    if (g > 8192) g = 8192;
-    return (int)(g < 1 ? 1 : g);
-}
+int grid_for(long long work) { return grid_for(work, 8192); }  // stage_util.h
 
 }  // namespace
 

@@ -23,6 +23,7 @@
 #include <limits.h>
 
 #include "common.h"
+#include "stage_util.h"
 
 // this file's own arithmetic is written as it is meant: nothing here may fuse (e = |d - gt| must see the rounded d)
 #pragma clang fp contract(off)
@@ -30,10 +31,10 @@
 namespace {
 
 constexpr int EX_BLOCKS = 128;  // partial rows per sample at most (grid-stride beyond)
-constexpr int EX_ROW = 8;
+constexpr int EX_ROW = row_walk::ROW;  // block_partial_row's
 
 __device__ __forceinline__ uint32_t disp_code(float v) {
-    if (!(fabsf(v) < INFINITY)) return 0u;  // NaN, +-inf
+    if (!finite_f(v)) return 0u;  // NaN, +-inf
     const double p = fmin(fmax((double)v * 1000.0, 0.0), 16646655.0);
     return (uint32_t)(int)rint(p);
 }
@@ -42,16 +43,6 @@ __device__ __forceinline__ uint32_t code_bytes(uint32_t c) {
     const uint32_t r = min(c / 65025u, 255u), rem = c - r * 65025u;
     const uint32_t g = min(rem / 255u, 255u), b = rem - g * 255u;
     return r | g << 8 | b << 16;
-}
-
-__device__ __forceinline__ void store_rgb4(uint8_t* dst, const uint32_t (&v)[4]) {  // 12 bytes, 4-B aligned
-    uint32_t* w = reinterpret_cast<uint32_t*>(dst);
-    w[0] = v[0] | v[1] << 24;               // r0 g0 b0 r1
-    w[1] = v[1] >> 8 | v[2] << 16;          // g1 b1 r2 g2
-    w[2] = v[2] >> 16 | v[3] << 8;          // b2 r3 g3 b3
-}
-__device__ __forceinline__ void store_rgb1(uint8_t* dst, uint32_t v) {
-    dst[0] = (uint8_t)v, dst[1] = (uint8_t)(v >> 8), dst[2] = (uint8_t)(v >> 16);
 }
 
 // Four consecutive pixels of a sample's [Hs][Ws] plane per thread (the last thread of an odd plane fewer). VEC: Ws % 4
@@ -87,7 +78,7 @@ __global__ __launch_bounds__(256) void k_disp_export(const float* __restrict__ d
                 }
                 if (partial != nullptr) {
                     const float gt = decode_rgb24(gt_rgb + (base + e) * 3);
-                    if (gt > 0.f && fabsf(d[p]) < INFINITY) {
+                    if (gt > 0.f && finite_f(d[p])) {
                         const float err = fabsf(d[p] - gt);
                         const double e64 = (double)err;
                         ++n;
@@ -102,40 +93,23 @@ __global__ __launch_bounds__(256) void k_disp_export(const float* __restrict__ d
             }
         }
         if (VEC) {
-            if (disp_rgb != nullptr) store_rgb4(disp_rgb + (base + e0) * 3, dc);
-            if (sigma_rgb != nullptr) store_rgb4(sigma_rgb + (base + e0) * 3, sc);
+            if (disp_rgb != nullptr) st_rgb<4>(disp_rgb + (base + e0) * 3, dc);
+            if (sigma_rgb != nullptr) st_rgb<4>(sigma_rgb + (base + e0) * 3, sc);
             if (disp_up != nullptr) *reinterpret_cast<float4*>(disp_up + base + e0) = make_float4(d[0], d[1], d[2], d[3]);
         } else {
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 if (p < cnt) {
-                    if (disp_rgb != nullptr) store_rgb1(disp_rgb + (base + e0 + p) * 3, dc[p]);
-                    if (sigma_rgb != nullptr) store_rgb1(sigma_rgb + (base + e0 + p) * 3, sc[p]);
+                    if (disp_rgb != nullptr) st_rgb1(disp_rgb + (base + e0 + p) * 3, dc[p]);
+                    if (sigma_rgb != nullptr) st_rgb1(sigma_rgb + (base + e0 + p) * 3, sc[p]);
                     if (disp_up != nullptr) disp_up[base + e0 + p] = d[p];
                 }
             }
         }
     }
     if (partial == nullptr) return;  // uniform over the grid
-    // the block's row: each wave by a shuffle tree, then the four waves in order (counts are exact as doubles)
-    double v[7] = {(double)n, se, se2, (double)c1, (double)c2, (double)c3, (double)cd};
-    __shared__ double red[4][EX_ROW];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) v[k] += __shfl_down(v[k], s);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 7; ++k) red[threadIdx.x >> 6][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < EX_ROW) {
-        const int k = threadIdx.x;
-        double t = 0.0;
-        if (k < 7) t = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-        partial[((size_t)b * gridDim.x + blockIdx.x) * EX_ROW + k] = t;
-    }
+    const double v[7] = {(double)n, se, se2, (double)c1, (double)c2, (double)c3, (double)cd};
+    block_partial_row<256>(v, partial + ((size_t)b * gridDim.x + blockIdx.x) * EX_ROW);
 }
 
 // metrics[b][k] = the sample's partial rows added in index order; one block of 64 threads per sample

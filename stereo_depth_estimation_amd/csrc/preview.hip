@@ -4,174 +4,46 @@
 //   quantile select : np.percentile(values, q) of the FINITE values of a map (zeros and negatives are members), exact,
 //                     on the device: a three-level radix select over full 32-bit keys
 //   compose         : the four panels of n samples in one launch
-// The select is the scheme of live.hip's sd_live_select (11 + 11 + 9 bits over the 31-bit patterns of finite positive
-// floats, fixed 2 % / 98 %) restated for this rule: every finite value, 32-bit keys through the monotone map (negative:
-// all bits flipped, else the sign bit set), 11 + 11 + 10 bits, and the two quantiles as arguments. live.hip is untouched.
+// The select is radix_select.h's, which sd_live_select shares (there: finite positive values, their 31-bit patterns as
+// keys, 11 + 11 + 9 bits, 2 % / 98 %, numpy's _lerp). This rule set: every finite value, 32-bit keys through the monotone
+// map (negative: all bits flipped, else the sign bit set), 11 + 11 + 10 bits, the two quantiles as arguments, a + d g.
 // No allocation, no synchronisation; integer atomics only, so a map's result does not depend on what else is in the
 // batch.
 #include <limits.h>
 #include <math.h>
 
 #include "common.h"
+#include "radix_select.h"
+#include "stage_util.h"
 
 // every rounding below is the one written: a * b + c stays two roundings
 #pragma clang fp contract(off)
 
 namespace {
 
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < INFINITY; }  // false for NaN
-
-// order-preserving key of a float: -x < -0.0 < +0.0 < x as unsigned integers
-__device__ __forceinline__ unsigned key_of(float x) {
-    const unsigned b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : b | 0x80000000u;
-}
-__device__ __forceinline__ float value_of(unsigned key) {
-    return __uint_as_float((key & 0x80000000u) ? key ^ 0x80000000u : ~key);
-}
-
 // ------------------------------------------------------------------ exact order statistics
-// Level 1 histograms the top 11 key bits of every finite value; a one-block scan finds, for each of the four wanted
-// ranks, the bin that holds it and the rank within the bin; level 2 histograms the next 11 bits of the values in those
-// bins, level 3 the last 10. Targets that share a prefix share a histogram. Histograms are built in LDS per block and
-// added to the global ones (non-zero bins only); counts are 32-bit. The last scan writes the result row and zeroes the
-// map's work buffer again.
-constexpr int QS_H1 = 0, QS_H2 = 2048, QS_H3 = QS_H2 + 4 * 2048, QS_STATE = QS_H3 + 4 * 1024;
-constexpr int QS_WORDS = QS_STATE + 16;  // state: n, prefix[4], rank[4]
-
-template <int LEVEL> struct QsLevel {
-    static constexpr int BINS = LEVEL == 3 ? 1024 : 2048, BITS = LEVEL == 3 ? 10 : 11, NH = LEVEL == 1 ? 1 : 4;
-    static constexpr int BASE = LEVEL == 1 ? QS_H1 : LEVEL == 2 ? QS_H2 : QS_H3;
+// radix_select.h's three-level select under this rule set: every finite value counts; 32-bit keys through the monotone
+// map, 11 + 11 + 10 bits.
+struct PreviewSelect {
+    static constexpr int LAST_BITS = 10;
+    __device__ __forceinline__ static bool member(float v) { return finite_f(v); }
+    // order-preserving key of a float: -x < -0.0 < +0.0 < x as unsigned integers
+    __device__ __forceinline__ static unsigned key(float x) {
+        const unsigned b = __float_as_uint(x);
+        return (b & 0x80000000u) ? ~b : b | 0x80000000u;
+    }
+    __device__ __forceinline__ static float value(unsigned key) {
+        return __uint_as_float((key & 0x80000000u) ? key ^ 0x80000000u : ~key);
+    }
+    // the percentile from the two order statistics around (n - 1) * q: v[k] + (v[k + 1] - v[k]) * g in fp64, rounded
+    // to float32 once
+    __device__ __forceinline__ static float lerp(float a, float b, double pos) {
+        const double g = pos - floor(pos);
+        const double d = (double)b - (double)a;
+        const double t = d * g;
+        return (float)((double)a + t);
+    }
 };
-
-// grid (blocks, m): work [m][QS_WORDS]
-template <int LEVEL>
-__global__ __launch_bounds__(256) void k_qs_hist(const float* __restrict__ values, int P, unsigned* __restrict__ work_all) {
-    using Lv = QsLevel<LEVEL>;
-    constexpr int BINS = Lv::BINS, NH = Lv::NH;
-    const float* __restrict__ v = values + (size_t)blockIdx.y * P;
-    unsigned* __restrict__ work = work_all + (size_t)blockIdx.y * QS_WORDS;
-    __shared__ unsigned h[NH * BINS];
-    for (int i = threadIdx.x; i < NH * BINS; i += 256) h[i] = 0u;
-    unsigned pf[4] = {0u, 0u, 0u, 0u};
-    bool own[4] = {true, false, false, false};
-    if (LEVEL > 1) {
-        if (work[QS_STATE] == 0u) return;  // no finite value (uniform over the map's blocks)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pf[j] = work[QS_STATE + 1 + j];
-#pragma unroll
-        for (int j = 1; j < 4; ++j) own[j] = pf[j] != pf[j - 1];
-    }
-    __syncthreads();
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < P; i += stride) {
-        const float x = v[i];
-        if (!finite_f(x)) continue;
-        const unsigned key = key_of(x);
-        if (LEVEL == 1) {
-            atomicAdd(&h[key >> 21], 1u);
-        } else {
-            const unsigned hi = LEVEL == 2 ? key >> 21 : key >> 10;
-            const unsigned lo = LEVEL == 2 ? (key >> 10) & 2047u : key & 1023u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (own[j] && hi == pf[j]) atomicAdd(&h[j * BINS + lo], 1u);
-        }
-    }
-    __syncthreads();
-    unsigned* g = work + Lv::BASE;
-    for (int i = threadIdx.x; i < NH * BINS; i += 256)
-        if (h[i]) atomicAdd(g + i, h[i]);
-}
-
-// the percentile from the two order statistics around (n - 1) * q: v[k] + (v[k + 1] - v[k]) * g in fp64, rounded to
-// float32 once
-__device__ __forceinline__ float lerp_q(float a, float b, double pos) {
-    const double g = pos - floor(pos);
-    const double d = (double)b - (double)a;
-    const double t = d * g;
-    return (float)((double)a + t);
-}
-
-// one block per map: sel [m][8]
-template <int LEVEL>
-__global__ __launch_bounds__(256) void k_qs_scan(unsigned* __restrict__ work_all, float* __restrict__ sel_all, double q_lo,
-                                                 double q_hi) {
-    using Lv = QsLevel<LEVEL>;
-    constexpr int BINS = Lv::BINS, PER = BINS / 256, BITS = Lv::BITS;
-    unsigned* __restrict__ work = work_all + (size_t)blockIdx.x * QS_WORDS;
-    float* __restrict__ sel = sel_all + (size_t)blockIdx.x * 8;
-    unsigned* st = work + QS_STATE;
-    __shared__ unsigned part[4][256];
-    __shared__ unsigned s_pf[4], s_rk[4], s_out[4], s_n;
-    const int t = threadIdx.x;
-    if (t < 4) {
-        s_pf[t] = LEVEL == 1 ? 0u : st[1 + t];
-        s_rk[t] = LEVEL == 1 ? 0u : st[5 + t];
-    }
-    if (t == 0) s_n = LEVEL == 1 ? 0u : st[0];
-    __syncthreads();
-    const unsigned* hist[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int src = j;
-        if (LEVEL > 1)
-            while (src > 0 && s_pf[src] == s_pf[src - 1]) --src;
-        hist[j] = work + Lv::BASE + (LEVEL == 1 ? 0 : src * BINS);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        unsigned sum = 0u;
-        for (int i = 0; i < PER; ++i) sum += hist[j][t * PER + i];
-        part[j][t] = sum;
-    }
-    __syncthreads();
-    if (LEVEL == 1 && t == 0) {
-        unsigned n = 0u;
-        for (int c = 0; c < 256; ++c) n += part[0][c];
-        s_n = n;
-        if (n > 0u) {
-            const unsigned klo = (unsigned)floor((double)(n - 1u) * q_lo), khi = (unsigned)floor((double)(n - 1u) * q_hi);
-            s_rk[0] = min(klo, n - 1u);
-            s_rk[1] = min(klo + 1u, n - 1u);
-            s_rk[2] = min(khi, n - 1u);
-            s_rk[3] = min(khi + 1u, n - 1u);
-        }
-    }
-    __syncthreads();
-    const unsigned n = s_n;
-    if (t < 4 && n > 0u) {
-        const unsigned r = s_rk[t];
-        unsigned cum = 0u;
-        int c = 0;
-        while (c < 255 && cum + part[t][c] <= r) cum += part[t][c++];
-        int b = c * PER;
-        while (b < c * PER + PER - 1 && cum + hist[t][b] <= r) cum += hist[t][b++];
-        s_out[t] = (s_pf[t] << BITS) | (unsigned)b;
-        st[1 + t] = s_out[t];
-        st[5 + t] = r - cum;
-    }
-    if (t == 0) st[0] = n;
-    if (LEVEL == 3) {
-        __syncthreads();  // the histograms were read: zero the whole work buffer for the next call
-        for (int i = t; i < QS_WORDS; i += 256) work[i] = 0u;
-        if (t == 0) {
-            reinterpret_cast<unsigned*>(sel)[0] = n;
-            if (n == 0u) {
-                for (int j = 1; j < 7; ++j) sel[j] = NAN;
-            } else {
-                const float a0 = value_of(s_out[0]), a1 = value_of(s_out[1]);
-                const float b0 = value_of(s_out[2]), b1 = value_of(s_out[3]);
-                sel[1] = a0;
-                sel[2] = a1;
-                sel[3] = b0;
-                sel[4] = b1;
-                sel[5] = lerp_q(a0, a1, (double)(n - 1u) * q_lo);
-                sel[6] = lerp_q(b0, b1, (double)(n - 1u) * q_hi);
-            }
-        }
-    }
-}
 
 // ------------------------------------------------------------------ montage
 // colour code of an input value: trunc(clip(float32(x * 255), 0, 255)); NaN -> 0 (fmaxf returns the other operand)
@@ -184,29 +56,6 @@ __device__ __forceinline__ uint8_t gray_of(float m, float vmin, float scale) {
     const float d = m - vmin;
     const float x = fminf(fmaxf(d / scale, 0.f), 1.f);
     return (uint8_t)(int)(x * 255.f);
-}
-
-template <int V> __device__ __forceinline__ void ld_f(const float* p, float (&v)[V]) {
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-        v[0] = p[0];
-    }
-}
-// V RGB pixels (3 V bytes): three 4-B stores for V = 4
-template <int V> __device__ __forceinline__ void st_rgb(uint8_t* p, const uint8_t (&c)[3 * V]) {
-    if constexpr (V == 4) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(p);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            q[k] = (uint32_t)c[4 * k] | (uint32_t)c[4 * k + 1] << 8 | (uint32_t)c[4 * k + 2] << 16 |
-                   (uint32_t)c[4 * k + 3] << 24;
-    } else {
-        p[0] = c[0];
-        p[1] = c[1];
-        p[2] = c[2];
-    }
 }
 
 // grid (blocks, n). One work item = V consecutive pixels of one panel row: item -> (y, panel, x). V = 4 needs W % 4 == 0
@@ -237,23 +86,23 @@ __global__ __launch_bounds__(256) void k_preview_compose(const float* __restrict
         const int r = (int)(it - (long long)y * 4 * WV);
         const int panel = r / WV, x = (r - panel * WV) * V;
         const size_t px = (size_t)y * W + x;
-        uint8_t c[3 * V];
+        uint32_t c[V];  // r | g << 8 | b << 16
         if (panel < 2) {
             float ch[3][V];
 #pragma unroll
             for (int k = 0; k < 3; ++k) ld_f<V>(inp + (size_t)(panel * 3 + k) * P + px, ch[k]);
 #pragma unroll
             for (int i = 0; i < V; ++i)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) c[3 * i + k] = colour_of(ch[k][i]);
+                c[i] = (uint32_t)colour_of(ch[0][i]) | (uint32_t)colour_of(ch[1][i]) << 8 |
+                       (uint32_t)colour_of(ch[2][i]) << 16;
         } else {
             const int j = panel - 2;
             float m[V];
             ld_f<V>(maps[j] + px, m);
 #pragma unroll
             for (int i = 0; i < V; ++i) {
-                const uint8_t g = any[j] ? gray_of(m[i], vmin[j], scale[j]) : (uint8_t)0;
-                c[3 * i] = c[3 * i + 1] = c[3 * i + 2] = g;
+                const uint32_t g = any[j] ? gray_of(m[i], vmin[j], scale[j]) : 0u;
+                c[i] = g | g << 8 | g << 16;
             }
         }
         st_rgb<V>(out + ((size_t)y * 4 * W + (size_t)panel * W + x) * 3, c);
@@ -261,17 +110,13 @@ __global__ __launch_bounds__(256) void k_preview_compose(const float* __restrict
 }
 
 // ------------------------------------------------------------------ host side
-bool aligned(const void* p, unsigned a) { return ((uintptr_t)p % a) == 0; }
 bool maps_ok(int m) { return m >= 1 && m <= 64; }
-int grid_for(long long work) {
-    long long g = (work + 255) / 256;
-    if (g > 2048) g = 2048;
-    return (int)(g < 1 ? 1 : g);
-}
 
 }  // namespace
 
-extern "C" long long sd_quantile_select_ws_bytes(int m) { return maps_ok(m) ? (long long)m * QS_WORDS * 4 : -1; }
+extern "C" long long sd_quantile_select_ws_bytes(int m) {
+    return maps_ok(m) ? (long long)m * SelectLayout<PreviewSelect>::WORDS * 4 : -1;
+}
 
 extern "C" int sd_quantile_select_n(int m, const float* values, int count, double q_lo, double q_hi, unsigned* work,
                                     float* sel, sd_stream s) {
@@ -280,15 +125,7 @@ extern "C" int sd_quantile_select_n(int m, const float* values, int count, doubl
     SD_REQUIRE(values && work && sel, "%s: null pointer (values, work, sel)", fn);
     SD_REQUIRE(count > 0, "%s: count %d", fn, count);
     SD_REQUIRE(q_lo >= 0.0 && q_lo <= q_hi && q_hi <= 1.0, "%s: quantiles %g, %g (0 <= q_lo <= q_hi <= 1)", fn, q_lo, q_hi);
-    const int blocks = cdiv(count, 1024) < 256 ? cdiv(count, 1024) : 256;
-    const dim3 g(blocks, m), g1(m), b(256);
-    hipStream_t st = to_stream(s);
-    hipLaunchKernelGGL(k_qs_hist<1>, g, b, 0, st, values, count, work);
-    hipLaunchKernelGGL(k_qs_scan<1>, g1, b, 0, st, work, sel, q_lo, q_hi);
-    hipLaunchKernelGGL(k_qs_hist<2>, g, b, 0, st, values, count, work);
-    hipLaunchKernelGGL(k_qs_scan<2>, g1, b, 0, st, work, sel, q_lo, q_hi);
-    hipLaunchKernelGGL(k_qs_hist<3>, g, b, 0, st, values, count, work);
-    hipLaunchKernelGGL(k_qs_scan<3>, g1, b, 0, st, work, sel, q_lo, q_hi);
+    select_launch<PreviewSelect>(m, values, count, q_lo, q_hi, work, sel, 0, to_stream(s));
     return sd_check_launch(fn);
 }
 
@@ -301,7 +138,7 @@ extern "C" int sd_preview_compose_n(int n, const float* input, const float* targ
     SD_REQUIRE(H > 0 && W > 0 && (long long)H * W <= INT_MAX / 16, "%s: bad sizes %dx%d", fn, H, W);
     const bool vec = W % 4 == 0 && aligned(input, 16) && aligned(target, 16) && aligned(pred, 16) && aligned(montage, 4);
     const long long items = (long long)H * 4 * (W / (vec ? 4 : 1));
-    hipLaunchKernelGGL(vec ? k_preview_compose<4> : k_preview_compose<1>, dim3(grid_for(items), n), dim3(256), 0,
+    hipLaunchKernelGGL(vec ? k_preview_compose<4> : k_preview_compose<1>, dim3(grid_for(items, 2048), n), dim3(256), 0,
                        to_stream(s), input, target, pred, H, W, sel_t, sel_p, montage);
     return sd_check_launch(fn);
 }

@@ -15,47 +15,29 @@
 //   gdisp       (w_photo / float32(N)) [cls == 0] dl/dd + (w_smooth / float32(M)) g_s, M = n H W
 // Three plain launches whatever n is: the normaliser N from the check stage's rows (one block; the values are exact
 // integers in fp64), the pass, the addition of the partial rows. The pass is the check stage's shape: a block owns whole
-// rows and walks them as one sequence in steps of SS_STEP pixels, four consecutive pixels per thread, 16-B loads and
-// stores when W % 4 == 0 and the pointers allow, scalar ones otherwise, the same pixels per thread either way. The stencil's
-// neighbours come from global memory (the rows above and below, and the two columns beside the thread's four), the
-// gradient is a gather: no atomics, no LDS but for the block's sums, no block waits for another. The sums of `rows`
-// have one fixed order: a thread adds its pixels in the order it meets them, a block adds its threads by a shuffle tree
-// and its four waves in order into one partial row in `work`, and the last launch adds a sample's partial rows.
+// rows and walks them as one sequence in steps of row_walk::STEP pixels (selfsup.STEP_PIXELS), four consecutive pixels
+// per thread, 16-B loads and stores when W % 4 == 0 and the pointers allow, scalar ones otherwise, the same pixels per
+// thread either way. The stencil's neighbours come from global memory (the rows above and below, and the two columns
+// beside the thread's four), the gradient is a gather: no atomics, no LDS but for the block's sums, no block waits for
+// another. The sums of `rows` have one fixed order: a thread adds its pixels in the order it meets them, a block adds
+// its threads into one partial row in `work` (block_partial_row), and the last launch adds a sample's partial rows
+// (k_rows_sum; both are stage_util.h's, shared with the check stage).
 // No allocation, no synchronisation: the entry point is graph-capturable. Workspace is the caller's.
 #include <float.h>
 #include <math.h>
 
 #include "common.h"
+#include "stage_util.h"
 
 // the restatement rounds every operation on its own: nothing here may fuse
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int SS_THREADS = 256;  // four waves
-constexpr int SS_PX = 4;         // consecutive pixels per thread
-constexpr int SS_STEP = SS_THREADS * SS_PX;  // pixels per step of the row walk (selfsup.STEP_PIXELS)
-constexpr int SS_MAX_BLOCKS = 1024;          // partial rows per sample at most
-constexpr int SS_SMALL_ROWS = 16;            // rows a block owns at most because W is small
-constexpr int SS_ROW = 8;
-constexpr int SS_HEAD = 8;           // doubles ahead of the partial rows in `work`: [0] the normaliser N
-constexpr int SS_SUM_THREADS = 512;  // of the launch that adds the partial rows: 64 partial rows x 8 columns a step
+// the row walk's shape, the sizes it accepts and the blocks it takes are stage_util.h's row_walk, as in the check stage
+constexpr int SS_THREADS = row_walk::THREADS, SS_PX = row_walk::PX, SS_ROW = row_walk::ROW;
+constexpr int SS_HEAD = 8;  // doubles ahead of the partial rows in `work`: [0] the normaliser N
 constexpr int SS_CNT_THREADS = 256;
-
-bool ss_sizes_ok(int n, int H, int W) {
-    return n >= 1 && n <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 31);
-}
-// rows per block and blocks per sample: functions of (H, W) alone, as in check.hip
-int ss_rows_per_block(int H, int W) {
-    int r = SS_STEP / W;
-    r = r < 1 ? 1 : (r > SS_SMALL_ROWS ? SS_SMALL_ROWS : r);
-    const int need = (H + SS_MAX_BLOCKS - 1) / SS_MAX_BLOCKS;
-    return r > need ? r : need;
-}
-int ss_blocks(int H, int W) {
-    const int r = ss_rows_per_block(H, W);
-    return (H + r - 1) / r;
-}
 
 struct SelfSupArgs {
     const float* disp;
@@ -71,13 +53,11 @@ struct SelfSupArgs {
     float eps2, eps_s2, gamma;
 };
 
-__device__ __forceinline__ bool ss_finite(float v) { return fabsf(v) <= FLT_MAX; }
-
 // One smoothness pair (p, q): its term and s; false (and both 0) when a disparity is not finite.
 __device__ __forceinline__ bool ss_pair(float dp, float dq, float lp0, float lp1, float lp2, float lq0, float lq1,
                                         float lq2, float gamma, float eps_s2, float& term, float& s) {
     term = 0.f, s = 0.f;
-    if (!(ss_finite(dp) && ss_finite(dq))) return false;
+    if (!(finite_f(dp) && finite_f(dq))) return false;
     const float t = dq - dp;
     const float g = __fdiv_rn((fabsf(lq0 - lp0) + fabsf(lq1 - lp1)) + fabsf(lq2 - lp2), 3.0f);
     const float w = expf(-(gamma * g));
@@ -91,8 +71,7 @@ __device__ __forceinline__ bool ss_pair(float dp, float dq, float lp0, float lp1
 template <bool VEC>
 __device__ __forceinline__ void ss_load4(const float* p, int cnt, float (&v)[SS_PX]) {
     if (VEC) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+        ld_f<SS_PX>(p, v);
     } else {
 #pragma unroll
         for (int i = 0; i < SS_PX; ++i)
@@ -123,7 +102,7 @@ __global__ __launch_bounds__(SS_CNT_THREADS) void k_selfsup_count(const double* 
 // stores, any width and alignment; the same pixels per thread, so the same bytes and the same sums. blockIdx.y = sample.
 template <bool VEC>
 __global__ __launch_bounds__(SS_THREADS) void k_selfsup_loss(SelfSupArgs a) {
-    const unsigned sid = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const unsigned sid = blockIdx.y, tid = threadIdx.x;
     const unsigned W = (unsigned)a.W;
     const size_t plane = (size_t)a.H * W;
     const float* in = a.input + (size_t)sid * 6 * plane;  // L_c = in + c * plane, R_c = in + (3 + c) * plane
@@ -242,7 +221,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_selfsup_loss(SelfSupArgs a) {
             if (okd) ss += (double)ty, ++n_pair;
             const float gs = (sxv[p] - sxv[p + 1]) + (syu - syd);
             float g = gp + a.ssm * gs;
-            if (!ss_finite(d)) g = 0.f;
+            if (!finite_f(d)) g = 0.f;
             gd[p] = g;
             sg += (double)fabsf(g);
         }
@@ -258,52 +237,15 @@ __global__ __launch_bounds__(SS_THREADS) void k_selfsup_loss(SelfSupArgs a) {
             }
         }
     }
-    // the block's row: each wave by a shuffle tree, then the four waves in order (counts are exact as doubles)
-    double v[6] = {(double)n_cnt, sl, se, ss, (double)n_pair, sg};
-    __shared__ double red[SS_THREADS / 64][SS_ROW];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) v[k] += __shfl_down(v[k], s);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) red[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (tid < SS_ROW) {
-        double t = 0.0;
-        if (tid < 6) t = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-        a.partial[((size_t)sid * gridDim.x + blockIdx.x) * SS_ROW + tid] = t;
-    }
-}
-
-// rows[b][k] = the sum of the sample's partial rows, in check.hip's order: thread (j, k) adds column k of the partial
-// rows j, j + 64, ..., a wave adds its eight j by shuffles and the eight waves are added in order.
-__global__ __launch_bounds__(SS_SUM_THREADS) void k_selfsup_rows(const double* __restrict__ partial, int nblk,
-                                                                 double* __restrict__ rows) {
-    const int b = blockIdx.x, k = threadIdx.x & (SS_ROW - 1), j = threadIdx.x >> 3;
-    const double* p = partial + (size_t)b * nblk * SS_ROW;
-    double t = 0.0;
-    for (int i = j; i < nblk; i += SS_SUM_THREADS / SS_ROW) t += p[(size_t)i * SS_ROW + k];
-#pragma unroll
-    for (int s = 32; s >= SS_ROW; s >>= 1) t += __shfl_down(t, s);
-    __shared__ double red[SS_SUM_THREADS / 64][SS_ROW];
-    if ((threadIdx.x & 63) < SS_ROW) red[threadIdx.x >> 6][k] = t;
-    __syncthreads();
-    if (threadIdx.x < SS_ROW) {
-        double sum = red[0][k];
-#pragma unroll
-        for (int w = 1; w < SS_SUM_THREADS / 64; ++w) sum += red[w][k];
-        rows[(size_t)b * SS_ROW + k] = sum;
-    }
+    const double v[6] = {(double)n_cnt, sl, se, ss, (double)n_pair, sg};
+    block_partial_row<SS_THREADS>(v, a.partial + ((size_t)sid * gridDim.x + blockIdx.x) * SS_ROW);
 }
 
 }  // namespace
 
 extern "C" long long sd_selfsup_ws_bytes(int n, int H, int W) {
-    if (!ss_sizes_ok(n, H, W)) return -1;
-    return ((long long)n * ss_blocks(H, W) * SS_ROW + SS_HEAD) * (long long)sizeof(double);
+    if (!row_walk::sizes_ok(n, H, W)) return -1;
+    return ((long long)n * row_walk::blocks(H, W) * SS_ROW + SS_HEAD) * (long long)sizeof(double);
 }
 
 extern "C" int sd_selfsup_loss(int n, const float* disp, const float* logvar, const float* input, const uint8_t* cls,
@@ -315,7 +257,7 @@ extern "C" int sd_selfsup_loss(int n, const float* disp, const float* logvar, co
     SD_REQUIRE(input, "sd_selfsup_loss: null input");
     SD_REQUIRE(cls, "sd_selfsup_loss: null cls (sd_stereo_check's classes of this disp)");
     SD_REQUIRE(check_rows, "sd_selfsup_loss: null check_rows (sd_stereo_check's rows of this disp)");
-    SD_REQUIRE(ss_sizes_ok(n, H, W), "sd_selfsup_loss: bad sizes H x W = %d x %d (positive, H * W < 2^31)", H, W);
+    SD_REQUIRE(row_walk::sizes_ok(n, H, W), "sd_selfsup_loss: bad sizes H x W = %d x %d (positive, H * W < 2^31)", H, W);
     SD_REQUIRE(w_photo >= 0.f && w_photo <= FLT_MAX, "sd_selfsup_loss: w_photo %g (finite and >= 0)", (double)w_photo);
     SD_REQUIRE(w_smooth >= 0.f && w_smooth <= FLT_MAX, "sd_selfsup_loss: w_smooth %g (finite and >= 0)",
                (double)w_smooth);
@@ -341,13 +283,13 @@ extern "C" int sd_selfsup_loss(int n, const float* disp, const float* logvar, co
     a.partial = static_cast<double*>(work) + SS_HEAD;
     a.H = H;
     a.W = W;
-    a.rows_per = ss_rows_per_block(H, W);
+    a.rows_per = row_walk::rows_per_block(H, W);
     a.w_photo = w_photo;
     a.ssm = w_smooth / (float)((long long)n * H * W);
     a.eps2 = eps * eps;
     a.eps_s2 = eps_s * eps_s;
     a.gamma = gamma;
-    const int nblk = ss_blocks(H, W);
+    const int nblk = row_walk::blocks(H, W);
     const bool vec = W % 4 == 0 && (uintptr_t)disp % 16 == 0 && (uintptr_t)logvar % 16 == 0 &&
                      (uintptr_t)input % 16 == 0 && (uintptr_t)cls % 4 == 0 && (uintptr_t)gdisp % 16 == 0 &&
                      (uintptr_t)glogvar % 16 == 0;
@@ -359,6 +301,7 @@ extern "C" int sd_selfsup_loss(int n, const float* disp, const float* logvar, co
         hipLaunchKernelGGL(k_selfsup_loss<true>, grid, block, 0, st, a);
     else
         hipLaunchKernelGGL(k_selfsup_loss<false>, grid, block, 0, st, a);
-    hipLaunchKernelGGL(k_selfsup_rows, dim3(n), dim3(SS_SUM_THREADS), 0, st, a.partial, nblk, rows);
+    hipLaunchKernelGGL((k_rows_sum<SS_ROW, row_walk::SUM_THREADS>), dim3(n), dim3(row_walk::SUM_THREADS), 0, st,
+                       a.partial, nblk, rows);
     return sd_check_launch("sd_selfsup_loss");
 }

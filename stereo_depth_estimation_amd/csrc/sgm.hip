@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "stage_util.h"
 
 // fp64 reprojection and display codes reproduce numpy's separately rounded operations
 #pragma clang fp contract(off)
@@ -821,55 +822,19 @@ __global__ __launch_bounds__(256) void k_sgm_code(const float* __restrict__ disp
     }
 }
 
-// np.nanmedian of the centre window (half = max(1, window / 2) around (H/2, W/2), clipped to the map): every non-NaN
-// value counts, infinities and negatives included (sd_live_center keeps only finite, > 0 values). Bitonic sort in LDS,
-// padded with +inf; even count: the float32 mean of the two middle values; no value: NaN.
+// np.nanmedian of the centre window: stage_util.h's center_median over every non-NaN value, infinities and negatives
+// included (sd_live_center keeps only finite, > 0 values).
+struct NotNaN {
+    __device__ __forceinline__ static bool test(float v) { return v == v; }
+};
 __global__ __launch_bounds__(256) void k_sgm_center(const float* __restrict__ src, int H, int W, int window,
                                                     float* __restrict__ out) {  // one block per stream
     if (const unsigned sid = stream_index(blockIdx.x)) {
         stream_branch();
         seek_stream(src, sid, (long long)H * W), out += sid;
     }
-    __shared__ float buf[4096];
-    __shared__ int s_cnt;
-    if (threadIdx.x == 0) s_cnt = 0;
-    const int cx = W / 2, cy = H / 2, half = max(1, window / 2);
-    const int y0 = max(0, cy - half), y1 = min(H, cy + half + 1), x0 = max(0, cx - half), x1 = min(W, cx + half + 1);
-    const int ww = x1 - x0, total = (y1 - y0) * ww;
-    int n2 = 64;
-    while (n2 < total) n2 <<= 1;
-    __syncthreads();
-    int mine = 0;
-    for (int i = threadIdx.x; i < n2; i += 256) {
-        float x = INFINITY;
-        if (i < total) {
-            const int r = i / ww;
-            x = src[(size_t)(y0 + r) * W + x0 + (i - r * ww)];
-            if (x == x) ++mine;
-            else x = INFINITY;
-        }
-        buf[i] = x;
-    }
-    if (mine) atomicAdd(&s_cnt, mine);
-    __syncthreads();
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n2; i += 256) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const float a = buf[i], b = buf[l];
-                    if ((a > b) == ((i & k) == 0)) {
-                        buf[i] = b;
-                        buf[l] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    if (threadIdx.x == 0) {
-        const int m = s_cnt;
-        out[0] = m == 0 ? NAN : (m & 1) ? buf[m / 2] : (buf[m / 2 - 1] + buf[m / 2]) / 2.f;
-    }
+    const float m = center_median<NotNaN>(src, H, W, window);
+    if (threadIdx.x == 0) out[0] = m;
 }
 
 // ------------------------------------------------------------------ launches

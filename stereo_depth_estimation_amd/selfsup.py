@@ -115,15 +115,6 @@ class SelfSupLoss:
         return {"w_photo": self.w_photo, "w_smooth": self.w_smooth, "eps": self.eps, "eps_s": self.eps_s,
                 "gamma": self.gamma, "occ_tol": self.occ_tol, "uncertainty": self.uncertainty}
 
-    def _grow(self, name: str, numel: int, dtype) -> torch.Tensor:
-        t = getattr(self, name)
-        if t is None or t.numel() < numel or t.device != self.device:
-            setattr(self, name, None)  # released before the larger one is made
-            with torch.inference_mode(False):
-                t = torch.empty(numel, dtype=dtype, device=self.device)
-            setattr(self, name, t)
-        return t
-
     def _bind_device(self, t: torch.Tensor):
         if self.device.index is None:
             self.device = torch.device("cuda", t.device.index)
@@ -137,8 +128,8 @@ class SelfSupLoss:
             raise ValueError(f"1..{self.streams} samples, got {n}")
         px = n * H * W
         with torch.cuda.device(self.device):
-            disp = self._grow("_disp", px, torch.float32)[:px].view(n, 1, H, W)
-            logvar = self._grow("_logvar", px, torch.float32)[:px].view(n, 1, H, W) if self.uncertainty else None
+            disp = L.grow(self, "_disp", px, torch.float32)[:px].view(n, 1, H, W)
+            logvar = L.grow(self, "_logvar", px, torch.float32)[:px].view(n, 1, H, W) if self.uncertainty else None
         return disp, logvar
 
     @property
@@ -206,12 +197,12 @@ class SelfSupLoss:
         px = n * H * W
         chk = self.check.run(disp, occ_tol=self.occ_tol, want=("cls", "rows"))
         with torch.cuda.device(self.device):
-            gdisp = self._grow("_gdisp", px, torch.float32)[:px].view(n, H, W)
-            glogvar = self._grow("_glogvar", px, torch.float32)[:px].view(n, H, W) if logvar is not None else None
-            rows = self._grow("_rows", self.streams * ROW, torch.float64)[:n * ROW].view(n, ROW)
-            work = self._grow("_work", L.call("sd_selfsup_ws_bytes", n, H, W) // 8, torch.float64)
+            gdisp = L.grow(self, "_gdisp", px, torch.float32)[:px].view(n, H, W)
+            glogvar = L.grow(self, "_glogvar", px, torch.float32)[:px].view(n, H, W) if logvar is not None else None
+            rows = L.grow(self, "_rows", self.streams * ROW, torch.float64)[:n * ROW].view(n, ROW)
+            work = L.grow(self, "_work", L.call("sd_selfsup_ws_bytes", n, H, W) // 8, torch.float64)
             if count is None:
-                count = self._grow("_count", 1, torch.int32)
+                count = L.grow(self, "_count", 1, torch.int32)
             if self._pin is None:
                 self._pin = torch.zeros(self.streams, ROW, dtype=torch.float64).pin_memory()
             L.call("sd_selfsup_loss", n, disp.data_ptr(), L.ptr(logvar), inputs.data_ptr(), chk.cls.data_ptr(),

@@ -152,6 +152,53 @@ def test_select_batch_equals_single_calls(L, m):
     assert np.array_equal(sel2.cpu().numpy()[:, :7].view(np.uint32), sel[:, :7].view(np.uint32)) and not work.any()
 
 
+def _two_rules_cases():
+    rng = np.random.default_rng(5)
+    return {
+        "37x53_wide": np.exp(rng.normal(0.0, 3.0, (37, 53))).astype(np.float32),  # a ragged last block
+        "160x200_narrow": (5.0 + 1e-4 * rng.random((160, 200))).astype(np.float32),  # four ranks in one level-1 bin
+        "1x1": np.array([[2.75]], dtype=np.float32),  # n = 1, 2: every rank clamped
+        "1x2": np.array([[9.5, 0.125]], dtype=np.float32),
+        "8x8_repeated": np.full((8, 8), 3.5, dtype=np.float32),
+    }
+
+
+TWO_RULES_CASES = _two_rules_cases()
+
+
+@pytest.mark.parametrize("name", list(TWO_RULES_CASES))
+def test_live_and_preview_rules_share_one_select(L, name):
+    """The two rule sets of the shared radix select on a map whose members are the same under both (finite, > 0):
+    sd_live_select_n and sd_quantile_select_n with q = 0.02, 0.98 agree on n and on the four order statistics bit for
+    bit. lo / hi follow each rule's own restatement (numpy's _lerp there, a + d g here; one float32 step, as the
+    tests of each stage allow), not each other. Each runs twice on its work buffer, which is zero again afterwards."""
+    m = TWO_RULES_CASES[name]
+    assert np.isfinite(m).all() and (m > 0).all()
+    h, w = m.shape
+    q = (0.02, 0.98)
+    dev = torch.device(DEV)
+    v = torch.as_tensor(m).to(dev)
+    s = L.stream_handle(dev)
+    work_l = torch.zeros(L.call("sd_live_select_n_ws_bytes", 1) // 4, dtype=torch.int32, device=dev)
+    work_p = torch.zeros(L.call("sd_quantile_select_ws_bytes", 1) // 4, dtype=torch.int32, device=dev)
+    sel_l, sel_p = torch.full((1, 8), 7.0, device=dev), torch.full((1, 8), 7.0, device=dev)
+    for _ in range(2):
+        L.call("sd_live_select_n", 1, v.data_ptr(), h, w, work_l.data_ptr(), sel_l.data_ptr(), None, 0, s)
+        L.call("sd_quantile_select_n", 1, v.data_ptr(), h * w, q[0], q[1], work_p.data_ptr(), sel_p.data_ptr(), s)
+    torch.cuda.synchronize()
+    assert not work_l.any() and not work_p.any()
+    live, prev = sel_l.cpu().numpy()[0], sel_p.cpu().numpy()[0]
+    assert int(live[:1].view(np.uint32)[0]) == int(prev[:1].view(np.uint32)[0]) == m.size
+    assert np.array_equal(live[1:5].view(np.uint32), prev[1:5].view(np.uint32)), (live[1:5], prev[1:5])
+    _check_sel(prev, m, q)
+    srt = np.sort(m.reshape(-1)).astype(np.float64)  # sd_live_select's lo, hi: tests/test_gpu_live.py _percentiles64
+    for got, qq in zip(live[5:7], q):
+        vi = (srt.size - 1) * qq
+        k = int(np.floor(vi))
+        a, b = srt[k], srt[min(k + 1, srt.size - 1)]
+        assert _within_one_step(got, np.float32(a + (b - a) * (vi - k))), (got, a, b, vi)
+
+
 # ---------------------------------------------------------------------------------------------------- montage
 def _device_montage(L, inp, tgt, pred):
     """The three ABI calls on a batch (numpy [n][6][H][W], [n][H][W] x 2) -> (montage u8, sel_t, sel_p) as numpy."""
