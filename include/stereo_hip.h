@@ -788,6 +788,31 @@ int sd_selfsup_loss(int n, const float* disp, const float* logvar, const float* 
                     const double* check_rows, int H, int W, float w_photo, float w_smooth, float eps, float eps_s,
                     float gamma, float* gdisp, float* glogvar, double* rows, int* count, void* work, sd_stream s);
 
+/* ---- the same loss with an SSIM term in the photometric error (SelfSupLoss(ssim=alpha); INTEGRATION.md
+ * "sd_selfsup_loss_ssim" is the normative text) ----
+ * sd_selfsup_loss's arguments, checks, alignment rules, count, N and M, with one more float32 parameter after gamma:
+ * alpha in [0, 1] (NaN and values outside are refused). The smoothness term, e and de/dd are sd_selfsup_loss's. With
+ * win(p) the pixels of p's sample at most one row and one column away, inside the image and with cls == 0 (k of them,
+ * every window sum started at 0 and taken in ascending (y, x) order), C1 = 0.01f 0.01f, C2 = 0.03f 0.03f, per channel:
+ *   muL = (sum L) / k, mur = (sum r) / k, sL = (sum (L - muL)^2) / k, sr = (sum (r - mur)^2) / k,
+ *   sLr = (sum (L - muL)(r - mur)) / k, A1 = 2 (muL mur) + C1, A2 = 2 sLr + C2, B1 = (muL muL + mur mur) + C1,
+ *   B2 = (sL + sr) + C2, S_c = (A1 A2) / (B1 B2)
+ *   s = (((1 - S_0) + (1 - S_1)) + (1 - S_2)) / 6, e' = (1 - alpha) e + alpha s; l and dl/dlv as before with e' for e
+ *   P = 2 ((muL A2) / (B1 B2) - (S mur) / B1), Qv = -(S / B2), T = (2 A1) / (B1 B2),
+ *   h_c(p, q) = ((P + (2 Qv)(r(q) - mur(p))) + T (L(q) - muL(p))) / k(p), u(p) = exp(-lv(p)) or 1,
+ *   g_ssim(q) = (((dba_0 sum_p u h_0) + dba_1 sum_p u h_1) + dba_2 sum_p u h_2) / 6 over p in win(q), dba_c = b_c - a_c
+ *   gdisp = (w_photo / float32(N)) [cls == 0] ((1 - alpha)(u de/dd) + alpha g_ssim) + (w_smooth / float32(M)) g_s
+ * rows [n][8]: as sd_selfsup_loss ([1] sum l with e', [2] sum e unchanged in meaning), [6] sum s, [7] 0.
+ * Three plain launches whatever n is; the pass is tiled (a block of 256 threads owns 32 x 16 pixels and stages them with
+ * a halo of two into LDS: the gradient is a gather, no atomics). One fixed summation order, a function of (n, H, W)
+ * alone; the vector and the scalar path give the same bytes. work: sd_selfsup_ssim_ws_bytes(n, H, W) bytes (64 of
+ * header, 64 per tile; -1 for sizes out of range; host only), 8-B aligned, needs no clearing. */
+long long sd_selfsup_ssim_ws_bytes(int n, int H, int W);
+int sd_selfsup_loss_ssim(int n, const float* disp, const float* logvar, const float* input, const uint8_t* cls,
+                         const double* check_rows, int H, int W, float w_photo, float w_smooth, float eps, float eps_s,
+                         float gamma, float alpha, float* gdisp, float* glogvar, double* rows, int* count, void* work,
+                         sd_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,6 +239,9 @@ PROTOTYPES: dict[str, tuple] = {
     # label-free adaptation: photometric + smoothness loss and its gradient for the heads' GRADS mode
     "sd_selfsup_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
     "sd_selfsup_loss": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _p]),
+    # the same with an SSIM term in the photometric error: one more float, alpha, after gamma
+    "sd_selfsup_ssim_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
+    "sd_selfsup_loss_ssim": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

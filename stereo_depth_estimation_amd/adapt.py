@@ -4,7 +4,7 @@
         (--left-dir DIR --right-dir DIR | --dataset-root DIR) --output-dir DIR \\
         [--height H --width W] [--epochs 1] [--batch-size 16] [--lr 1e-5] [--weight-decay 0] [--precision fp32|bf16] \\
         [--w-smooth 0.1] [--edge-gamma 10] [--occ-tol 0.5] [--no-uncertainty] [--max-samples 0] [--seed 42] \\
-        [--base-channels 32] [--read-threads 16] [--device cuda]
+        [--base-channels 32] [--read-threads 16] [--device cuda] [--ssim-weight 0]
 
 Runs ``selfsup.adapt_epoch`` over the pairs: the photometric + smoothness objective of ``sd_selfsup_loss`` (selfsup.py,
 INTEGRATION.md "sd_selfsup_loss") through the model's training forward, the hand-scheduled backward and AdamW. The frames
@@ -17,6 +17,11 @@ the trainer's ``--resume`` read), and ``<output-dir>/adapt_meta.json``, also pri
 epoch ``loss``, ``photo``, ``smooth`` and ``visible_fraction``, and the photometric loss of the first and the last epoch.
 With ``--dataset-root`` the labels are not used for training; they measure it: the EPE over the samples (``sd_disp_export``'s
 metric rows, as ``predict`` evaluates) is recorded before and after. ``--device cpu`` is rejected (no CPU path).
+
+``--ssim-weight A`` (0..1, default 0) mixes the SSIM dissimilarity of a 3 x 3 window into the photometric error,
+``(1 - A) e + A s`` (``SelfSupLoss(ssim=A)``, ``sd_selfsup_loss_ssim``): for rigs whose two sensors differ in gain or
+exposure. 0.85 is the literature's mix, not an optimum measured here. With A > 0 the epochs also carry ``ssim``, the mean
+s over the counted pixels, and the meta ``ssim_first`` / ``ssim_last``.
 """
 
 from __future__ import annotations
@@ -31,7 +36,7 @@ import torch
 
 from . import _lib as L
 from .check import check_params
-from .selfsup import SelfSupLoss, adapt_epoch, selfsup_params
+from .selfsup import SelfSupLoss, adapt_epoch, selfsup_params, ssim_param
 
 META_KEYS = ("loss", "photo", "smooth", "visible_fraction")
 
@@ -60,6 +65,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--base-channels", type=int, default=32)
     p.add_argument("--read-threads", type=int, default=16, help="Host threads of the PNG reader.")
     p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--ssim-weight", type=float, default=0.0,
+                   help="Weight A in [0, 1] of the SSIM term in the photometric error, (1 - A) e + A s (0: none; 0.85 is "
+                        "the literature's mix, not a measured optimum).")
     return p
 
 
@@ -74,7 +82,7 @@ def adapt_options(left_dir=None, right_dir=None, dataset_root=None, output_dir=N
                   epochs: int = 1, batch_size: int = 16, lr: float = 1e-5, weight_decay: float = 0.0,
                   precision: str = "fp32", w_smooth: float = 0.1, edge_gamma: float = 10.0, occ_tol: float = 0.5,
                   uncertainty: bool = True, max_samples: int = 0, seed: int = 42, base_channels: int = 32,
-                  read_threads: int = 16) -> dict:
+                  read_threads: int = 16, ssim_weight: float = 0.0) -> dict:
     """The tool's options checked and gathered (raises ValueError), before a model or a device is touched."""
     dirs = left_dir is not None or right_dir is not None
     if (dataset_root is not None) == dirs or (dirs and (left_dir is None or right_dir is None)):
@@ -102,12 +110,16 @@ def adapt_options(left_dir=None, right_dir=None, dataset_root=None, output_dir=N
         occ_tol, _ = check_params(occ_tol, float("inf"))
     except ValueError as e:
         raise ValueError(f"--w-smooth / --edge-gamma / --occ-tol: {e}") from None
+    try:
+        ssim_weight = ssim_param(ssim_weight)
+    except ValueError as e:
+        raise ValueError(f"--ssim-weight: {e}") from None
     return dict(left_dir=None if left_dir is None else str(left_dir), right_dir=None if right_dir is None else str(right_dir),
                 dataset_root=None if dataset_root is None else str(dataset_root), output_dir=str(output_dir),
                 height=height, width=width, epochs=int(epochs), batch_size=int(batch_size), lr=float(lr),
                 weight_decay=float(weight_decay), precision=precision, w_smooth=w_smooth, edge_gamma=edge_gamma,
                 occ_tol=occ_tol, uncertainty=bool(uncertainty), max_samples=int(max_samples), seed=int(seed),
-                base_channels=int(base_channels), read_threads=int(read_threads))
+                base_channels=int(base_channels), read_threads=int(read_threads), ssim_weight=ssim_weight)
 
 
 class _Frames:
@@ -262,13 +274,14 @@ def adapt(checkpoint, *, model=None, device="cuda", **options) -> dict:
     before = _measure_epe(model, frames, batches, H, W) if has_gt else None
     optimizer = FusedAdamW(model.parameters(), lr=opts["lr"], weight_decay=opts["weight_decay"])
     loss = SelfSupLoss(opts["batch_size"], w_smooth=opts["w_smooth"], gamma=opts["edge_gamma"], occ_tol=opts["occ_tol"],
-                       uncertainty=opts["uncertainty"], device=dev)
+                       uncertainty=opts["uncertainty"], device=dev, ssim=opts["ssim_weight"])
+    keys = META_KEYS + (("ssim",) if opts["ssim_weight"] > 0 else ())
     rng = np.random.default_rng(opts["seed"])
     epochs = []
     for _ in range(opts["epochs"]):
         order = [int(i) for i in rng.permutation(len(batches))]
         means = adapt_epoch(model, _InputLoader(frames, batches, H, W, order), dev, optimizer, loss)
-        epochs.append({k: means[k] for k in META_KEYS})
+        epochs.append({k: means[k] for k in keys})
     after = _measure_epe(model, frames, batches, H, W) if has_gt else None
     model.train(False)
     save_checkpoint(out_dir / "adapted.pt", int(ck.get("epoch", 0)), model, optimizer, _train_config(ck, opts),
@@ -278,6 +291,7 @@ def adapt(checkpoint, *, model=None, device="cuda", **options) -> dict:
             **{f"loss_{k}": v for k, v in loss.describe().items() if k in ("w_photo", "eps", "eps_s")},
             "rectified": True, "num_samples": len(items), "num_batches": len(batches), "epochs_run": epochs,
             "photo_first": epochs[0]["photo"], "photo_last": epochs[-1]["photo"],
+            **({"ssim_first": epochs[0]["ssim"], "ssim_last": epochs[-1]["ssim"]} if opts["ssim_weight"] > 0 else {}),
             "epe_before": before["epe"] if before else None, "epe_after": after["epe"] if after else None,
             "output": str(out_dir / "adapted.pt"), "elapsed_seconds": time.time() - started_at,
             "created_at_unix": time.time()}
@@ -292,7 +306,8 @@ def main(argv=None) -> dict:
     try:
         opts = adapt_options(a.left_dir, a.right_dir, a.dataset_root, a.output_dir, a.height, a.width, a.epochs,
                              a.batch_size, a.lr, a.weight_decay, a.precision, a.w_smooth, a.edge_gamma, a.occ_tol,
-                             not a.no_uncertainty, a.max_samples, a.seed, a.base_channels, a.read_threads)
+                             not a.no_uncertainty, a.max_samples, a.seed, a.base_channels, a.read_threads,
+                             a.ssim_weight)
     except ValueError as e:
         parser.error(str(e))
     _resolve_device(a.device)

@@ -27,6 +27,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "selfsup_px.h"
 #include "stage_util.h"
 
 // the restatement rounds every operation on its own: nothing here may fuse
@@ -35,9 +36,9 @@
 namespace {
 
 // the row walk's shape, the sizes it accepts and the blocks it takes are stage_util.h's row_walk, as in the check stage
-constexpr int SS_THREADS = row_walk::THREADS, SS_PX = row_walk::PX, SS_ROW = row_walk::ROW;
-constexpr int SS_HEAD = 8;  // doubles ahead of the partial rows in `work`: [0] the normaliser N
-constexpr int SS_CNT_THREADS = 256;
+// (the normaliser launch, the warp, the Charbonnier error and the smoothness pair are selfsup_px.h's, shared with
+// sd_selfsup_loss_ssim)
+constexpr int SS_THREADS = row_walk::THREADS, SS_PX = row_walk::PX;
 
 struct SelfSupArgs {
     const float* disp;
@@ -53,20 +54,6 @@ struct SelfSupArgs {
     float eps2, eps_s2, gamma;
 };
 
-// One smoothness pair (p, q): its term and s; false (and both 0) when a disparity is not finite.
-__device__ __forceinline__ bool ss_pair(float dp, float dq, float lp0, float lp1, float lp2, float lq0, float lq1,
-                                        float lq2, float gamma, float eps_s2, float& term, float& s) {
-    term = 0.f, s = 0.f;
-    if (!(finite_f(dp) && finite_f(dq))) return false;
-    const float t = dq - dp;
-    const float g = __fdiv_rn((fabsf(lq0 - lp0) + fabsf(lq1 - lp1)) + fabsf(lq2 - lp2), 3.0f);
-    const float w = expf(-(gamma * g));
-    const float r = __fsqrt_rn(t * t + eps_s2);
-    term = w * r;
-    s = __fdiv_rn(w * t, r);
-    return true;
-}
-
 // four consecutive floats at p (cnt of them inside the row); the rest stay 0
 template <bool VEC>
 __device__ __forceinline__ void ss_load4(const float* p, int cnt, float (&v)[SS_PX]) {
@@ -76,24 +63,6 @@ __device__ __forceinline__ void ss_load4(const float* p, int cnt, float (&v)[SS_
 #pragma unroll
         for (int i = 0; i < SS_PX; ++i)
             if (i < cnt) v[i] = p[i];
-    }
-}
-
-// N = max(1, sum_i (rows[i][0] - rows[i][1] - rows[i][2] - rows[i][6])) over the check stage's rows: exact integers in
-// fp64 below 2^53, so the strided chains and the tree give the sum in index order. count = that sum as int32
-// (saturated), 0 when nothing is counted.
-__global__ __launch_bounds__(SS_CNT_THREADS) void k_selfsup_count(const double* __restrict__ check_rows, int n,
-                                                                  double* __restrict__ nrm, int* __restrict__ count) {
-    double t = 0.0;
-    for (int i = threadIdx.x; i < n; i += SS_CNT_THREADS) {
-        const double* r = check_rows + (size_t)i * SS_ROW;
-        t += ((r[0] - r[1]) - r[2]) - r[6];
-    }
-    double z = 0.0;
-    block_sum2<SS_CNT_THREADS>(t, z);
-    if (threadIdx.x == 0) {
-        nrm[0] = t < 1.0 ? 1.0 : t;
-        count[0] = t < 1.0 ? 0 : (t > 2147483647.0 ? 2147483647 : (int)t);
     }
 }
 
@@ -179,23 +148,9 @@ __global__ __launch_bounds__(SS_THREADS) void k_selfsup_loss(SelfSupArgs a) {
             // photometric term of a counted pixel
             float gp = 0.f;
             if (cl[p] == 0u) {
-                const float xr = (float)(xb + p) - d;
-                const int xf = (int)floorf(xr);
-                const unsigned x0 = (unsigned)min(max(xf, 0), (int)W - 1), x1 = min(x0 + 1u, W - 1u);
-                const float f = xr - (float)x0;
-                float phi[3], q[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float* rp = in + (3 + c) * plane + rowp;
-                    const float ra = rp[x0], rb = rp[x1];
-                    const float dba = rb - ra;
-                    const float r = ra + f * dba;
-                    const float t = lc[c][p + 1] - r;
-                    phi[c] = __fsqrt_rn(t * t + a.eps2);
-                    q[c] = __fdiv_rn(t, phi[c]) * dba;
-                }
-                const float e = __fdiv_rn((phi[0] + phi[1]) + phi[2], 3.0f);
-                const float de = __fdiv_rn((q[0] + q[1]) + q[2], 3.0f);
+                float r[3], dba[3], e, de;
+                ss_warp(in + 3 * plane + rowp, plane, xb + p, W, d, r, dba);
+                ss_charbonnier(lc[0][p + 1], lc[1][p + 1], lc[2][p + 1], r, dba, a.eps2, e, de);
                 float l = e, dl = de;
                 if (has_lv) {
                     const float v = expf(-lv[p]);

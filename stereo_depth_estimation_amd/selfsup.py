@@ -15,6 +15,13 @@ first-order smoothness term runs over every pixel pair. The arithmetic is ``sd_s
 INTEGRATION.md "sd_selfsup_loss"); it is held to the NumPy restatement tests/selfsup_ref.py. Kernels: csrc/selfsup.hip.
 There is no CPU fallback.
 
+``SelfSupLoss(..., ssim=0.85)`` mixes a structural term into the photometric error, e' = (1 - ssim) e + ssim s with s
+the SSIM dissimilarity of the 3 x 3 window of counted pixels around each pixel: two sensors of a real rig never agree in
+gain, exposure or white balance, which gives an absolute colour difference a floor that no disparity removes, whereas
+SSIM compares local structure and is largely insensitive to gain and offset. The stage is then ``sd_selfsup_loss_ssim``
+(csrc/selfsup_ssim.hip, INTEGRATION.md "sd_selfsup_loss_ssim", restated in tests/selfsup_ssim_ref.py). The default is 0:
+the stage and every byte are then ``sd_selfsup_loss``'s. 0.85 is the literature's mix, not an optimum measured here.
+
 The frames are taken as rectified: a pixel (x, y) of the left frame is looked for at (x - d, y) of the right frame. The
 defaults (``w_photo`` = 1, ``w_smooth`` = 0.1, ``eps`` = ``eps_s`` = 0.01, ``gamma`` = 10, ``occ_tol`` = 0.5 px) are
 parameters and not measured optima: how much smoothness a scene bears, and how sharp an image edge must be before a
@@ -34,6 +41,10 @@ from .check import StereoCheck, check_params
 MAX_SAMPLES = 65535
 STEP_PIXELS = 1024  # csrc/selfsup.hip SS_STEP: pixels per step of a block's walk over its rows, four per thread
 ROW = 8             # doubles per sample: counted, sum l, sum e, sum smoothness terms, pairs, sum |gdisp|, 0, 0
+                    # (with ssim > 0: [6] sum s)
+SSIM_TILE_W, SSIM_TILE_H = 32, 16  # csrc/selfsup_ssim.hip SSIM_TW, SSIM_TH: the pixels a block of the tiled pass owns
+ROW_SSIM = 6        # the column of ``rows`` that holds sum s
+TOTAL_SSIM = 8      # sum s over every run rides behind ``totals`` in the same buffer
 SUMMARY_KEYS = ("loss", "photo", "smooth", "visible_fraction", "grad_l1")
 # totals: the columns of ``rows`` summed over every sample of every step, then [6] steps and [7] pixels
 TOTAL_STEPS, TOTAL_PIXELS = 6, 7
@@ -50,6 +61,14 @@ def selfsup_params(w_photo=1.0, w_smooth=0.1, eps=0.01, eps_s=0.01, gamma=10.0) 
             raise ValueError(f"{name} must be finite and {'> 0' if strict else '>= 0'}, got {v}")
         out.append(f)
     return tuple(out)
+
+
+def ssim_param(ssim=0.0) -> float:
+    """The weight of the SSIM term as the float32 value the kernel computes with: in [0, 1]."""
+    f = float(np.float32(ssim))
+    if not 0.0 <= f <= 1.0:  # NaN fails both comparisons
+        raise ValueError(f"ssim must be in [0, 1], got {ssim}")
+    return f
 
 
 def summary_from_rows(rows, pixels: int, w_photo: float, w_smooth: float) -> dict:
@@ -74,28 +93,36 @@ class SelfSupResult:
     count:   int32 [1], the counted pixels of the batch (the AdamW gate reads it)
     cls:     uint8 [n, H, W], the geometry-only classes of ``check.CLASSES``"""
 
-    __slots__ = ("gdisp", "glogvar", "rows", "count", "cls", "_pin", "_device", "_w")
+    __slots__ = ("gdisp", "glogvar", "rows", "count", "cls", "_pin", "_device", "_w", "_ssim")
 
-    def __init__(self, gdisp, glogvar, rows, count, cls, pin, device, w):
+    def __init__(self, gdisp, glogvar, rows, count, cls, pin, device, w, ssim=False):
         self.gdisp, self.glogvar, self.rows, self.count, self.cls = gdisp, glogvar, rows, count, cls
-        self._pin, self._device, self._w = pin, device, w
+        self._pin, self._device, self._w, self._ssim = pin, device, w, ssim
 
     def summary(self) -> dict:
-        """The dict of ``SUMMARY_KEYS`` over the batch. One copy of ``rows`` through a pinned buffer and the only host
+        """The dict of ``SUMMARY_KEYS`` over the batch (with ``ssim`` > 0 also ``"ssim"``, the mean s over the counted
+        pixels, None when nothing counted). One copy of ``rows`` through a pinned buffer and the only host
         synchronisation."""
         n = self.rows.shape[0]
         self._pin[:n].copy_(self.rows, non_blocking=True)
         torch.cuda.current_stream(self._device).synchronize()
-        return summary_from_rows(self._pin[:n].numpy().copy(), self.gdisp.numel(), *self._w)
+        rows = self._pin[:n].numpy().copy()
+        out = summary_from_rows(rows, self.gdisp.numel(), *self._w)
+        if self._ssim:
+            counted = float(rows[:, 0].sum())
+            out["ssim"] = float(rows[:, ROW_SSIM].sum()) / counted if counted > 0 else None
+        return out
 
 
 class SelfSupLoss:
     """``sd_stereo_check`` (geometry only) and ``sd_selfsup_loss`` with their buffers: up to ``streams`` (1..65535)
     samples of one size per call, five launches whatever their number. Buffers are made once per size and only grow;
-    ``run`` issues launches only. ``totals`` accumulates the rows of every run on the device; ``means()`` reads them."""
+    ``run`` issues launches only. ``totals`` accumulates the rows of every run on the device; ``means()`` reads them.
+    ``ssim`` in [0, 1] is the weight of the SSIM term in the photometric error (0: none, and ``sd_selfsup_loss`` as it
+    always was; above 0 the stage is ``sd_selfsup_loss_ssim``; 0.85 is the literature's mix, not a measured optimum)."""
 
     def __init__(self, streams: int = 1, w_photo=1.0, w_smooth=0.1, eps=0.01, eps_s=0.01, gamma=10.0, occ_tol=0.5,
-                 uncertainty: bool = True, device="cuda"):
+                 uncertainty: bool = True, device="cuda", ssim=0.0):
         n = int(streams)
         if not 1 <= n <= MAX_SAMPLES:
             raise ValueError(f"streams must be in [1, {MAX_SAMPLES}], got {streams}")
@@ -103,6 +130,7 @@ class SelfSupLoss:
         self.w_photo, self.w_smooth, self.eps, self.eps_s, self.gamma = selfsup_params(w_photo, w_smooth, eps, eps_s,
                                                                                        gamma)
         self.occ_tol, _ = check_params(occ_tol, math.inf)
+        self.ssim = ssim_param(ssim)
         self.uncertainty = bool(uncertainty)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -112,8 +140,11 @@ class SelfSupLoss:
         self._count = self._pin = self._totals = self._inc = self._tpin = None
 
     def describe(self) -> dict:
-        return {"w_photo": self.w_photo, "w_smooth": self.w_smooth, "eps": self.eps, "eps_s": self.eps_s,
-                "gamma": self.gamma, "occ_tol": self.occ_tol, "uncertainty": self.uncertainty}
+        out = {"w_photo": self.w_photo, "w_smooth": self.w_smooth, "eps": self.eps, "eps_s": self.eps_s,
+               "gamma": self.gamma, "occ_tol": self.occ_tol, "uncertainty": self.uncertainty}
+        if self.ssim != 0:
+            out["ssim"] = self.ssim
+        return out
 
     def _bind_device(self, t: torch.Tensor):
         if self.device.index is None:
@@ -135,31 +166,41 @@ class SelfSupLoss:
     @property
     def totals(self) -> torch.Tensor:
         """float64 [8] on the device: the columns of ``rows`` summed over every sample of every ``run`` since
-        ``reset()``, then the number of runs and of pixels."""
+        ``reset()``, then the number of runs and of pixels. A view of a buffer of nine doubles: the ninth is the sum of
+        s (``ssim`` > 0), so that ``means()`` stays one copy."""
         if self._totals is None:
             with torch.inference_mode(False):
-                self._totals = torch.zeros(ROW, dtype=torch.float64, device=self.device)
+                self._totals9 = torch.zeros(ROW + 1, dtype=torch.float64, device=self.device)
+                self._totals = self._totals9[:ROW]
                 self._inc = torch.zeros(ROW, dtype=torch.float64, device=self.device)
         return self._totals
 
     def reset(self):
-        self.totals.zero_()
+        self.totals  # noqa: B018 (makes the buffer)
+        self._totals9.zero_()
 
     def means(self, since=None) -> dict | None:
         """``summary_from_rows`` of the totals (minus ``since``, an earlier host copy of them), pixel-weighted over the
-        runs, plus ``steps``; None when nothing ran. One pinned copy, one synchronisation."""
+        runs, plus ``steps`` and, with ``ssim`` > 0, ``ssim``: the mean s over the counted pixels; None when nothing ran.
+        One pinned copy, one synchronisation. ``last_totals`` is the host copy to hand back as ``since`` (with ``ssim``
+        > 0 it carries the sum of s as a ninth value)."""
         if self._tpin is None:
-            self._tpin = torch.zeros(ROW, dtype=torch.float64).pin_memory()
-        self._tpin.copy_(self.totals, non_blocking=True)
+            self._tpin = torch.zeros(ROW + 1, dtype=torch.float64).pin_memory()
+        self.totals  # noqa: B018 (makes the buffer)
+        self._tpin.copy_(self._totals9, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
-        t = self._tpin.numpy().copy()
-        self.last_totals = t
+        t9 = self._tpin.numpy().copy()
+        self.last_totals = (t9 if self.ssim != 0 else t9[:ROW]).copy()
         if since is not None:
-            t = t - np.asarray(since, dtype=np.float64)
+            since = np.asarray(since, dtype=np.float64)
+            t9[:len(since)] -= since
+        t = t9[:ROW]
         if t[TOTAL_STEPS] <= 0:
             return None
         out = summary_from_rows(t, int(t[TOTAL_PIXELS]), self.w_photo, self.w_smooth)
         out["steps"] = int(t[TOTAL_STEPS])
+        if self.ssim != 0:
+            out["ssim"] = float(t9[TOTAL_SSIM]) / float(t[0]) if t[0] > 0 else None
         return out
 
     def run(self, disp: torch.Tensor, logvar: torch.Tensor | None, inputs: torch.Tensor,
@@ -200,22 +241,33 @@ class SelfSupLoss:
             gdisp = L.grow(self, "_gdisp", px, torch.float32)[:px].view(n, H, W)
             glogvar = L.grow(self, "_glogvar", px, torch.float32)[:px].view(n, H, W) if logvar is not None else None
             rows = L.grow(self, "_rows", self.streams * ROW, torch.float64)[:n * ROW].view(n, ROW)
-            work = L.grow(self, "_work", L.call("sd_selfsup_ws_bytes", n, H, W) // 8, torch.float64)
+            ws = "sd_selfsup_ssim_ws_bytes" if self.ssim != 0 else "sd_selfsup_ws_bytes"
+            work = L.grow(self, "_work", L.call(ws, n, H, W) // 8, torch.float64)
             if count is None:
                 count = L.grow(self, "_count", 1, torch.int32)
             if self._pin is None:
                 self._pin = torch.zeros(self.streams, ROW, dtype=torch.float64).pin_memory()
-            L.call("sd_selfsup_loss", n, disp.data_ptr(), L.ptr(logvar), inputs.data_ptr(), chk.cls.data_ptr(),
-                   chk.rows.data_ptr(), H, W, self.w_photo, self.w_smooth, self.eps, self.eps_s, self.gamma,
-                   gdisp.data_ptr(), L.ptr(glogvar), rows.data_ptr(), count.data_ptr(), work.data_ptr(),
-                   L.stream_handle(self.device))
-            # the per-interval sums: rows[6..7] are 0, so the steps and pixels ride in those two slots
+            head = (n, disp.data_ptr(), L.ptr(logvar), inputs.data_ptr(), chk.cls.data_ptr(), chk.rows.data_ptr(), H, W,
+                    self.w_photo, self.w_smooth, self.eps, self.eps_s, self.gamma)
+            tail = (gdisp.data_ptr(), L.ptr(glogvar), rows.data_ptr(), count.data_ptr(), work.data_ptr(),
+                    L.stream_handle(self.device))
             totals = self.totals
-            with torch.no_grad():
-                totals.add_(rows.sum(dim=0))
-                self._add_step(px)
+            if self.ssim != 0:
+                L.call("sd_selfsup_loss_ssim", *head, self.ssim, *tail)
+                # rows[6] is the sum of s here: it goes behind the totals, whose [6] and [7] stay steps and pixels
+                with torch.no_grad():
+                    sums = rows.sum(dim=0)
+                    self._totals9[:ROW_SSIM].add_(sums[:ROW_SSIM])
+                    self._totals9[TOTAL_SSIM:].add_(sums[ROW_SSIM:ROW_SSIM + 1])
+                    self._add_step(px)
+            else:
+                L.call("sd_selfsup_loss", *head, *tail)
+                # the per-interval sums: rows[6..7] are 0, so the steps and pixels ride in those two slots
+                with torch.no_grad():
+                    totals.add_(rows.sum(dim=0))
+                    self._add_step(px)
         return SelfSupResult(gdisp, glogvar, rows, count, chk.cls, self._pin, self.device,
-                             (self.w_photo, self.w_smooth))
+                             (self.w_photo, self.w_smooth), self.ssim != 0)
 
     def _add_step(self, px: int):
         """totals[6] += 1, totals[7] += px, without a host-to-device copy per run: the increment vector is refilled only
@@ -253,7 +305,7 @@ def adapt_step(model, optimizer, inputs: torch.Tensor, loss: SelfSupLoss) -> Sel
 def adapt_epoch(model, loader, device, optimizer, loss: SelfSupLoss, log_every_batches: int | None = None, logger=None):
     """``adapt_step`` over the batches ``{"input": float32 [n, 6, H, W]}`` of ``loader`` (any other key is ignored: labels
     are not used). Returns the epoch's pixel-weighted means (``SelfSupLoss.means``: loss, photo, smooth,
-    visible_fraction, grad_l1, steps). The sums are read once per ``log_every_batches`` steps (``logger.log_metrics``,
+    visible_fraction, grad_l1, steps; ssim when the loss has the term). The sums are read once per ``log_every_batches`` steps (``logger.log_metrics``,
     as ``run_epoch``) and once at the end."""
     model.train(True)
     loss._bind_device(torch.empty(0, device=device))

@@ -16,7 +16,13 @@ Second figure: ms per ``adapt_step`` against ms per ``train_step`` of the full-w
 same process in alternating rounds; ``train_step`` is the parent's, so their difference is what the label-free objective
 costs over the supervised one.
 
+With ``--ssim A`` (say 0.85, the literature's mix) the same figures are also taken for the loss with the SSIM term
+(``SelfSupLoss(ssim=A)``, ``sd_selfsup_loss_ssim``): the stage beside the plain one and beside the same loss in torch ops
+(window moments by ``avg_pool2d``-style shifted sums of the masked planes) with autograd, and ``adapt_step`` with the
+term beside ``adapt_step`` without it, all in the same alternating rounds.
+
     python tools/selfsup_bench.py --json profiles/selfsup_bench.json
+    python tools/selfsup_bench.py --ssim 0.85 --json profiles/selfsup_ssim_bench.json
 """
 
 from __future__ import annotations
@@ -79,7 +85,27 @@ def scene(H: int, W: int, n: int, dev):
     return disp, logvar, x
 
 
-def torch_loss(disp, logvar, x, occ_tol: float, p: dict):
+def _box(v, m, H, W):
+    """The sum of the masked plane over the 3 x 3 window around every pixel."""
+    q = torch.nn.functional.pad(v * m, (1, 1, 1, 1))
+    return sum(q[..., i:i + H, j:j + W] for i in range(3) for j in range(3))
+
+
+def torch_ssim(left, r, vis):
+    """s per pixel in torch ops: the SSIM dissimilarity over the window's counted pixels."""
+    H, W = left.shape[-2:]
+    m = vis[:, None].float()
+    k = _box(torch.ones_like(m), m, H, W).clamp(min=1)
+    muL, mur = _box(left, m, H, W) / k, _box(r, m, H, W) / k
+    sL = _box(left * left, m, H, W) / k - muL * muL
+    sr = _box(r * r, m, H, W) / k - mur * mur
+    sLr = _box(left * r, m, H, W) / k - muL * mur
+    c1, c2 = 0.01 ** 2, 0.03 ** 2
+    S = ((2 * muL * mur + c1) * (2 * sLr + c2)) / ((muL * muL + mur * mur + c1) * (sL + sr + c2))
+    return (1 - S).sum(dim=1) / 6
+
+
+def torch_loss(disp, logvar, x, occ_tol: float, p: dict, ssim: float = 0.0):
     """The baseline: the geometry-only classes and the loss in torch ops (float32), autograd for the gradients. Returns
     (gdisp, glogvar, loss, counted)."""
     n, H, W = disp.shape
@@ -103,8 +129,11 @@ def torch_loss(disp, logvar, x, occ_tol: float, p: dict):
     left, right = x[:, :3], x[:, 3:]
     a = torch.gather(right, 3, x0[:, None].expand(-1, 3, -1, -1))
     b = torch.gather(right, 3, x1[:, None].expand(-1, 3, -1, -1))
-    t = left - (a + f[:, None] * (b - a))
+    r = a + f[:, None] * (b - a)
+    t = left - r
     e = torch.sqrt(t * t + p["eps"] ** 2).sum(dim=1) / 3
+    if ssim > 0:
+        e = (1 - ssim) * e + ssim * torch_ssim(left, r, vis)
     ell = e * torch.exp(-lv) + lv
     photo = torch.where(vis, ell, zero).sum() / N
     smooth = zero
@@ -142,7 +171,31 @@ def bench_stage(a, dev) -> list:
         ms_graph = _graph_ms(stage, a.iters)
         ms, t_ms = statistics.median(ms_s), statistics.median(ms_t)
         moved = n * H * W * BYTES_PER_PIXEL
-        out.append({"H": H, "W": W, "samples": n, "pixels": n * H * W, **PARAMS, "occ_tol": 0.5,
+        extra = {}
+        if a.ssim > 0:
+            # the same rounds for the loss with the SSIM term, beside the plain stage's of this process
+            loss_s = selfsup.SelfSupLoss(n, device=dev, ssim=a.ssim, **PARAMS)
+            stage_s = lambda: loss_s.run(disp, logvar, x)  # noqa: E731
+            base_s = lambda: torch_loss(disp, logvar, x, 0.5, PARAMS, a.ssim)  # noqa: E731
+            res_s, ref_s = stage_s(), base_s()
+            sum_s = res_s.summary()
+            gd_s = float((res_s.gdisp - ref_s[0]).abs().max()) / float(ref_s[0].abs().max())
+            _events(stage_s, a.warmup, a.warmup)
+            _events(base_s, 3, 3)
+            r_s, r_p, r_t = [], [], []
+            for _ in range(a.rounds):
+                r_s.append(_events(stage_s, a.iters, 0)[0])
+                r_p.append(_events(stage, a.iters, 0)[0])
+                r_t.append(_events(base_s, a.torch_iters, 0)[0])
+            m_s, m_p, m_t = statistics.median(r_s), statistics.median(r_p), statistics.median(r_t)
+            extra = {"ssim": a.ssim, "ssim_mean_s": sum_s["ssim"], "ssim_loss": sum_s["loss"],
+                     "ssim_torch_loss": float(ref_s[2]), "ssim_ms_per_call": m_s, "ssim_ms_per_call_rounds": r_s,
+                     "plain_ms_per_call_same_rounds": m_p, "ssim_over_plain": m_s / m_p,
+                     "ssim_ms_per_call_graph_replay": _graph_ms(stage_s, a.iters),
+                     "ssim_torch_ms_per_call": m_t, "ssim_torch_ms_per_call_rounds": r_t,
+                     "ssim_speedup_vs_torch": m_t / m_s, "ssim_gdisp_max_diff_vs_torch_rel": gd_s}
+            del loss_s, res_s, ref_s
+        out.append({"H": H, "W": W, "samples": n, "pixels": n * H * W, **PARAMS, "occ_tol": 0.5, **extra,
                     "visible_fraction": s["visible_fraction"], "loss": s["loss"], "torch_loss": float(ref[2]),
                     "counted": int(res.count.item()), "torch_counted": int(ref[3]),
                     "ms_per_call": ms, "ms_per_call_rounds": ms_s, "ms_per_call_wall": statistics.median(wall_s),
@@ -172,16 +225,26 @@ def bench_step(a, dev) -> dict:
     loss = selfsup.SelfSupLoss(B, device=dev, **PARAMS)
     sup = lambda: train_step(m, opt, b["input"], b["target"], b["valid_mask"])  # noqa: E731
     ada = lambda: selfsup.adapt_step(m, opt, b["input"], loss)  # noqa: E731
+    loss_s = selfsup.SelfSupLoss(B, device=dev, ssim=a.ssim, **PARAMS) if a.ssim > 0 else None
+    ada_s = lambda: selfsup.adapt_step(m, opt, b["input"], loss_s)  # noqa: E731
     _events(sup, a.step_warmup, a.step_warmup)
     _events(ada, a.step_warmup, a.step_warmup)
-    ms_sup, ms_ada = [], []
+    if loss_s is not None:
+        _events(ada_s, a.step_warmup, a.step_warmup)
+    ms_sup, ms_ada, ms_ada_s = [], [], []
     for _ in range(a.rounds):
         ms_sup.append(_events(sup, a.step_iters, 0)[0])
         ms_ada.append(_events(ada, a.step_iters, 0)[0])
+        if loss_s is not None:
+            ms_ada_s.append(_events(ada_s, a.step_iters, 0)[0])
     s, d = statistics.median(ms_sup), statistics.median(ms_ada)
     out = {"batch": B, "H": H, "W": W, "precision": "bf16", "base_channels": 32, "train_step_ms": s,
            "train_step_ms_rounds": ms_sup, "adapt_step_ms": d, "adapt_step_ms_rounds": ms_ada,
            "adapt_minus_train_ms": d - s, "adapt_over_train": d / s, "means": loss.means()}
+    if loss_s is not None:
+        ds = statistics.median(ms_ada_s)
+        out.update({"ssim": a.ssim, "adapt_step_ssim_ms": ds, "adapt_step_ssim_ms_rounds": ms_ada_s,
+                    "adapt_ssim_minus_adapt_ms": ds - d, "adapt_ssim_over_adapt": ds / d, "ssim_means": loss_s.means()})
     print(json.dumps(out))
     return out
 
@@ -194,6 +257,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--step-warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--ssim", type=float, default=0.0,
+                    help="Also measure the loss with this SSIM weight (0.85 is the literature's mix, not an optimum).")
     ap.add_argument("--json", type=str, default=None, help="Write the results here.")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
