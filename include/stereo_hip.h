@@ -813,6 +813,44 @@ int sd_selfsup_loss_ssim(int n, const float* disp, const float* logvar, const fl
                          float gamma, float alpha, float* gdisp, float* glogvar, double* rows, int* count, void* work,
                          sd_stream s);
 
+/* ---- proxy-label adaptation: the matcher's labels as a sparse target of the heads, alone or on top of the label-free
+ * loss (stereo_depth_estimation_amd/proxy.py; INTEGRATION.md "sd_proxy_gray" and "sd_proxy_loss" are the normative
+ * text) ----
+ * sd_proxy_gray: the model's input batch back to the gray images of the matcher. n samples (1..65535) of one size,
+ * H * W < 2^31: input f32 [n][6][H][W] planar (left RGB / 255, then right), gray_l and gray_r u8 [n][H][W]. Per channel
+ * value x: b = (int) rintf(min(max(x 255, 0), 255)) in float32 (ties to even; a NaN gives 0), then the matcher's step 1
+ * on the bytes with channel 0 as R: g = (4899 R + 9617 G + 1868 B + 8192) >> 14. An input that is float32(b / 255) gives
+ * b back. One launch, the sample a grid dimension; 16-B loads and 4-B stores when W % 4 == 0, input is 16-B and the
+ * outputs are 4-B aligned, scalar accesses otherwise, the same bytes either way. */
+int sd_proxy_gray(int n, const float* input, int H, int W, uint8_t* gray_l, uint8_t* gray_r, sd_stream s);
+
+/* sd_proxy_loss: n samples (1..65535) of one size, H * W < 2^31: disp f32 [n][H][W], the heads' output; logvar f32
+ * [n][H][W] or NULL; proxy_q4 i16 [n][H][W], 16 * disparity as the matcher writes it, required; w_proxy finite and
+ * >= 0; accumulate 0 or 1. All in float32, every operation rounded on its own:
+ *   labelled    q4 > 0 and disp finite (the matcher's invalid value and a disparity of 0 are no label)
+ *   Np          max(1, labelled pixels of the batch), counted exactly; *count = that number as int32 (accumulate = 1:
+ *               plus what *count held), saturated at 2^31 - 1
+ *   per pixel   t = float32(q4) / 16, a = |disp - t|, sgn = 1, -1 or 0 (disp == t); l = a, dl/dd = sgn without
+ *               logvar, else v = exp(-lv): l = a v + lv, dl/dd = sgn v, dl/dlv = 1 - a v
+ *   g_d         (w_proxy / float32(Np)) dl/dd, g_lv = (w_proxy / float32(Np)) dl/dlv
+ * Outputs:
+ *   gdisp   f32 [n][H][W]  accumulate = 0: g_d, 0 where the pixel is not labelled, every pixel written; accumulate = 1:
+ *                          gdisp + g_d at a labelled pixel, an unlabelled pixel is not written
+ *   glogvar f32 [n][H][W]  optional, only with logvar: the same with g_lv
+ *   rows    f64 [n][8]     [0] labelled pixels, [1] sum l, [2] sum a, [3] sum a^2 (each square exact in fp64),
+ *                          [4] sum |g_d|, [5] pixels with q4 > 0 and a non-finite disp, [6..7] 0
+ * The loss g_d and g_lv are the gradient of is w_proxy * sum_i rows[i][1] / Np. One fixed summation order, a function of
+ * (n, H, W) alone, no atomics: two runs give the same bits, and sample i's bytes depend on its neighbours only through
+ * Np. Four plain launches whatever n is (the blocks' counts, Np, the pass, the addition of the partial rows), the sample
+ * a grid dimension. Four pixels per thread with 16-B and 8-B accesses when W % 4 == 0, disp, logvar, gdisp, glogvar are
+ * 16-B and proxy_q4 is 8-B aligned; scalar ones otherwise; the same bytes either way. work: sd_proxy_ws_bytes(n, H, W)
+ * bytes (64 of header, 64 per block), 8-B aligned, needs no clearing (-1 for n outside 1..65535, non-positive sizes,
+ * H * W >= 2^31; host only). Arguments are checked before any launch; no allocation, no synchronisation,
+ * graph-capturable. */
+long long sd_proxy_ws_bytes(int n, int H, int W);
+int sd_proxy_loss(int n, const float* disp, const float* logvar, const int16_t* proxy_q4, int H, int W, float w_proxy,
+                  int accumulate, float* gdisp, float* glogvar, double* rows, int* count, void* work, sd_stream s);
+
 #ifdef __cplusplus
 }
 #endif

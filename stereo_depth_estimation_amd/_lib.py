@@ -242,6 +242,10 @@ PROTOTYPES: dict[str, tuple] = {
     # the same with an SSIM term in the photometric error: one more float, alpha, after gamma
     "sd_selfsup_ssim_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
     "sd_selfsup_loss_ssim": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _p]),
+    # proxy-label adaptation: the matcher's gray images from the model's input, and the sparse-label loss
+    "sd_proxy_gray": (_i, [_i, _p, _i, _i, _p, _p, _p]),
+    "sd_proxy_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
+    "sd_proxy_loss": (_i, [_i, _p, _p, _p, _i, _i, _f, _i, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

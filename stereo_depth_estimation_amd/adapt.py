@@ -4,7 +4,8 @@
         (--left-dir DIR --right-dir DIR | --dataset-root DIR) --output-dir DIR \\
         [--height H --width W] [--epochs 1] [--batch-size 16] [--lr 1e-5] [--weight-decay 0] [--precision fp32|bf16] \\
         [--w-smooth 0.1] [--edge-gamma 10] [--occ-tol 0.5] [--no-uncertainty] [--max-samples 0] [--seed 42] \\
-        [--base-channels 32] [--read-threads 16] [--device cuda] [--ssim-weight 0]
+        [--base-channels 32] [--read-threads 16] [--device cuda] [--ssim-weight 0] \\
+        [--proxy-weight 0] [--proxy-only] [--proxy-num-disparities 64] [--proxy-block-size 5] [--proxy-mode 3way]
 
 Runs ``selfsup.adapt_epoch`` over the pairs: the photometric + smoothness objective of ``sd_selfsup_loss`` (selfsup.py,
 INTEGRATION.md "sd_selfsup_loss") through the model's training forward, the hand-scheduled backward and AdamW. The frames
@@ -22,6 +23,14 @@ metric rows, as ``predict`` evaluates) is recorded before and after. ``--device 
 ``(1 - A) e + A s`` (``SelfSupLoss(ssim=A)``, ``sd_selfsup_loss_ssim``): for rigs whose two sensors differ in gain or
 exposure. 0.85 is the literature's mix, not an optimum measured here. With A > 0 the epochs also carry ``ssim``, the mean
 s over the counted pixels, and the meta ``ssim_first`` / ``ssim_last``.
+
+``--proxy-weight W`` (default 0: off) adds proxy supervision (proxy.py, INTEGRATION.md "sd_proxy_loss"): the device
+semi-global matcher labels the pixels it is sure of on every batch, and the heads are trained on those labels in the
+reference's NLL form beside the photometric term, with weight W. ``--proxy-only`` trains on the labels alone (no check
+stage, no photometric stage). ``--proxy-num-disparities`` (64), ``--proxy-block-size`` (5) and ``--proxy-mode`` (3way)
+are the matcher's; they are parameters, not measured optima. The batch size is then at most 64 (the matcher's streams)
+and the width must exceed the disparity range. With W > 0 the meta gains the proxy arguments, the epochs ``proxy_loss``,
+``proxy_mae`` and ``proxy_fraction``, and the meta ``proxy_mae_first`` / ``proxy_mae_last``.
 """
 
 from __future__ import annotations
@@ -36,9 +45,12 @@ import torch
 
 from . import _lib as L
 from .check import check_params
+from .proxy import MAX_STREAMS as PROXY_MAX_BATCH, check_width, proxy_param
 from .selfsup import SelfSupLoss, adapt_epoch, selfsup_params, ssim_param
 
 META_KEYS = ("loss", "photo", "smooth", "visible_fraction")
+PROXY_META_KEYS = ("proxy_loss", "proxy_mae", "proxy_fraction")
+PROXY_DEFAULTS = dict(proxy_num_disparities=64, proxy_block_size=5, proxy_mode="3way")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -68,6 +80,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ssim-weight", type=float, default=0.0,
                    help="Weight A in [0, 1] of the SSIM term in the photometric error, (1 - A) e + A s (0: none; 0.85 is "
                         "the literature's mix, not a measured optimum).")
+    p.add_argument("--proxy-weight", type=float, default=0.0,
+                   help="Weight of the proxy-label term: the device matcher's labels as a sparse target (0: off; a "
+                        "parameter, not a measured optimum).")
+    p.add_argument("--proxy-only", action="store_true", help="Train on the matcher's labels alone (needs --proxy-weight).")
+    p.add_argument("--proxy-num-disparities", type=int, default=None,
+                   help="Disparity range of the labelling matcher (default 64; a multiple of 16).")
+    p.add_argument("--proxy-block-size", type=int, default=None, help="Block size of the labelling matcher (default 5).")
+    p.add_argument("--proxy-mode", type=str, default=None, help="Path mode of the labelling matcher (default 3way).")
     return p
 
 
@@ -82,8 +102,10 @@ def adapt_options(left_dir=None, right_dir=None, dataset_root=None, output_dir=N
                   epochs: int = 1, batch_size: int = 16, lr: float = 1e-5, weight_decay: float = 0.0,
                   precision: str = "fp32", w_smooth: float = 0.1, edge_gamma: float = 10.0, occ_tol: float = 0.5,
                   uncertainty: bool = True, max_samples: int = 0, seed: int = 42, base_channels: int = 32,
-                  read_threads: int = 16, ssim_weight: float = 0.0) -> dict:
-    """The tool's options checked and gathered (raises ValueError), before a model or a device is touched."""
+                  read_threads: int = 16, ssim_weight: float = 0.0, proxy_weight: float = 0.0, proxy_only: bool = False,
+                  proxy_num_disparities=None, proxy_block_size=None, proxy_mode=None) -> dict:
+    """The tool's options checked and gathered (raises ValueError), before a model or a device is touched. The proxy
+    options are part of the result only with a positive ``proxy_weight``."""
     dirs = left_dir is not None or right_dir is not None
     if (dataset_root is not None) == dirs or (dirs and (left_dir is None or right_dir is None)):
         raise ValueError("give either --dataset-root or both --left-dir and --right-dir")
@@ -114,12 +136,48 @@ def adapt_options(left_dir=None, right_dir=None, dataset_root=None, output_dir=N
         ssim_weight = ssim_param(ssim_weight)
     except ValueError as e:
         raise ValueError(f"--ssim-weight: {e}") from None
+    proxy = _proxy_options(proxy_weight, proxy_only, proxy_num_disparities, proxy_block_size, proxy_mode, batch_size,
+                           width)
     return dict(left_dir=None if left_dir is None else str(left_dir), right_dir=None if right_dir is None else str(right_dir),
                 dataset_root=None if dataset_root is None else str(dataset_root), output_dir=str(output_dir),
                 height=height, width=width, epochs=int(epochs), batch_size=int(batch_size), lr=float(lr),
                 weight_decay=float(weight_decay), precision=precision, w_smooth=w_smooth, edge_gamma=edge_gamma,
                 occ_tol=occ_tol, uncertainty=bool(uncertainty), max_samples=int(max_samples), seed=int(seed),
-                base_channels=int(base_channels), read_threads=int(read_threads), ssim_weight=ssim_weight)
+                base_channels=int(base_channels), read_threads=int(read_threads), ssim_weight=ssim_weight, **proxy)
+
+
+def _proxy_options(weight, only, num_disparities, block_size, mode, batch_size, width) -> dict:
+    """The proxy options checked: {} with the weight at 0 (no other proxy option may then be given)."""
+    from .sgm import StereoSGM
+
+    try:
+        weight = proxy_param(weight)
+    except ValueError as e:
+        raise ValueError(f"--proxy-weight: {e}") from None
+    given = dict(proxy_num_disparities=num_disparities, proxy_block_size=block_size, proxy_mode=mode)
+    if weight == 0:
+        if only:
+            raise ValueError("--proxy-only needs a positive --proxy-weight")
+        extra = [f"--{k.replace('_', '-')}" for k, v in given.items() if v is not None]
+        if extra:
+            raise ValueError(f"{', '.join(extra)}: the matcher's options need a positive --proxy-weight")
+        return {}
+    out = {k: PROXY_DEFAULTS[k] if v is None else v for k, v in given.items()}
+    try:
+        m = StereoSGM(num_disparities=out["proxy_num_disparities"], block_size=out["proxy_block_size"],
+                      mode=out["proxy_mode"])
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"--proxy-num-disparities / --proxy-block-size / --proxy-mode: {e}") from None
+    if int(batch_size) > PROXY_MAX_BATCH:
+        raise ValueError(f"--batch-size must be <= {PROXY_MAX_BATCH} with --proxy-weight (the matcher's streams), "
+                         f"got: {batch_size}")
+    if width is not None:
+        try:
+            check_width(width, m.min_disparity, m.num_disparities)
+        except ValueError as e:
+            raise ValueError(f"--width / --proxy-num-disparities: {e}") from None
+    return dict(proxy_weight=weight, proxy_only=bool(only), proxy_num_disparities=m.num_disparities,
+                proxy_block_size=m.block_size, proxy_mode=m.mode)
 
 
 class _Frames:
@@ -273,25 +331,40 @@ def adapt(checkpoint, *, model=None, device="cuda", **options) -> dict:
     frames = _Frames(dev, opts["batch_size"], has_gt, opts["read_threads"])
     before = _measure_epe(model, frames, batches, H, W) if has_gt else None
     optimizer = FusedAdamW(model.parameters(), lr=opts["lr"], weight_decay=opts["weight_decay"])
-    loss = SelfSupLoss(opts["batch_size"], w_smooth=opts["w_smooth"], gamma=opts["edge_gamma"], occ_tol=opts["occ_tol"],
-                       uncertainty=opts["uncertainty"], device=dev, ssim=opts["ssim_weight"])
-    keys = META_KEYS + (("ssim",) if opts["ssim_weight"] > 0 else ())
+    use_proxy = opts.get("proxy_weight", 0.0) > 0
+    proxy = None
+    if use_proxy:
+        from .proxy import ProxyLoss
+
+        check_width(W, 0, opts["proxy_num_disparities"])
+        proxy = ProxyLoss(opts["batch_size"], w_proxy=opts["proxy_weight"], uncertainty=opts["uncertainty"], device=dev,
+                          num_disparities=opts["proxy_num_disparities"], block_size=opts["proxy_block_size"],
+                          mode=opts["proxy_mode"])
+    loss = None
+    if not (use_proxy and opts["proxy_only"]):
+        loss = SelfSupLoss(opts["batch_size"], w_smooth=opts["w_smooth"], gamma=opts["edge_gamma"],
+                           occ_tol=opts["occ_tol"], uncertainty=opts["uncertainty"], device=dev, ssim=opts["ssim_weight"])
+    keys = (META_KEYS + (("ssim",) if opts["ssim_weight"] > 0 else ()) if loss is not None else ()) \
+        + (PROXY_META_KEYS if use_proxy else ())
     rng = np.random.default_rng(opts["seed"])
     epochs = []
     for _ in range(opts["epochs"]):
         order = [int(i) for i in rng.permutation(len(batches))]
-        means = adapt_epoch(model, _InputLoader(frames, batches, H, W, order), dev, optimizer, loss)
+        means = adapt_epoch(model, _InputLoader(frames, batches, H, W, order), dev, optimizer, loss, proxy=proxy)
         epochs.append({k: means[k] for k in keys})
     after = _measure_epe(model, frames, batches, H, W) if has_gt else None
     model.train(False)
     save_checkpoint(out_dir / "adapted.pt", int(ck.get("epoch", 0)), model, optimizer, _train_config(ck, opts),
                     {f"adapt_{k}": v for k, v in epochs[-1].items() if v is not None},
                     global_step=int(ck.get("global_step", 0)))
+    described = loss.describe() if loss is not None else {}
     meta = {"format_version": 1, "checkpoint": str(checkpoint) if checkpoint is not None else None, **opts,
-            **{f"loss_{k}": v for k, v in loss.describe().items() if k in ("w_photo", "eps", "eps_s")},
+            **{f"loss_{k}": v for k, v in described.items() if k in ("w_photo", "eps", "eps_s")},
             "rectified": True, "num_samples": len(items), "num_batches": len(batches), "epochs_run": epochs,
-            "photo_first": epochs[0]["photo"], "photo_last": epochs[-1]["photo"],
-            **({"ssim_first": epochs[0]["ssim"], "ssim_last": epochs[-1]["ssim"]} if opts["ssim_weight"] > 0 else {}),
+            "photo_first": epochs[0].get("photo"), "photo_last": epochs[-1].get("photo"),
+            **({"ssim_first": epochs[0]["ssim"], "ssim_last": epochs[-1]["ssim"]}
+               if opts["ssim_weight"] > 0 and loss is not None else {}),
+            **({"proxy_mae_first": epochs[0]["proxy_mae"], "proxy_mae_last": epochs[-1]["proxy_mae"]} if use_proxy else {}),
             "epe_before": before["epe"] if before else None, "epe_after": after["epe"] if after else None,
             "output": str(out_dir / "adapted.pt"), "elapsed_seconds": time.time() - started_at,
             "created_at_unix": time.time()}
@@ -307,7 +380,9 @@ def main(argv=None) -> dict:
         opts = adapt_options(a.left_dir, a.right_dir, a.dataset_root, a.output_dir, a.height, a.width, a.epochs,
                              a.batch_size, a.lr, a.weight_decay, a.precision, a.w_smooth, a.edge_gamma, a.occ_tol,
                              not a.no_uncertainty, a.max_samples, a.seed, a.base_channels, a.read_threads,
-                             a.ssim_weight)
+                             a.ssim_weight, proxy_weight=a.proxy_weight, proxy_only=a.proxy_only,
+                             proxy_num_disparities=a.proxy_num_disparities, proxy_block_size=a.proxy_block_size,
+                             proxy_mode=a.proxy_mode)
     except ValueError as e:
         parser.error(str(e))
     _resolve_device(a.device)

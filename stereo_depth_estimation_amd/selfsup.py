@@ -22,6 +22,9 @@ SSIM compares local structure and is largely insensitive to gain and offset. The
 (csrc/selfsup_ssim.hip, INTEGRATION.md "sd_selfsup_loss_ssim", restated in tests/selfsup_ssim_ref.py). The default is 0:
 the stage and every byte are then ``sd_selfsup_loss``'s. 0.85 is the literature's mix, not an optimum measured here.
 
+``adapt_step(..., proxy=ProxyLoss(...))`` adds proxy supervision (proxy.py): the semi-global matcher labels the pixels
+it is sure of, and their gradient is added onto this loss's maps; ``loss=None`` trains on the labels alone.
+
 The frames are taken as rectified: a pixel (x, y) of the left frame is looked for at (x - d, y) of the right frame. The
 defaults (``w_photo`` = 1, ``w_smooth`` = 0.1, ``eps`` = ``eps_s`` = 0.01, ``gamma`` = 10, ``occ_tol`` = 0.5 px) are
 parameters and not measured optima: how much smoothness a scene bears, and how sharp an image edge must be before a
@@ -280,46 +283,84 @@ class SelfSupLoss:
         self._totals.add_(self._inc)
 
 
-def adapt_step(model, optimizer, inputs: torch.Tensor, loss: SelfSupLoss) -> SelfSupResult:
+def adapt_step(model, optimizer, inputs: torch.Tensor, loss: SelfSupLoss | None, proxy=None):
     """The label-free sibling of ``train_step``: one training step of ``model`` on ``inputs`` (float32 [n, 6, H, W] on
     the device) against ``loss``, in train mode, fp32 or bf16. Weight packs, the training forward, the heads into the
     loss object's maps, the geometry-only check, ``sd_selfsup_loss`` (its count into the engine's current count slot),
     the heads' GRADS mode, the hand-scheduled backward and AdamW, gated on the device by that count: a batch without a
-    counted pixel leaves the weights alone. No host synchronisation. The sums accumulate in ``loss.totals``."""
+    counted pixel leaves the weights alone. No host synchronisation. The sums accumulate in ``loss.totals``.
+
+    ``proxy``: a ``proxy.ProxyLoss`` whose matcher labels train the heads as well. After ``loss.run`` its gradient is
+    added onto the loss's maps and its labelled pixels onto the count, so the gate opens when either stage found pixels;
+    the result is the loss's (its maps then hold the sum), the proxy's own is ``proxy.last``. ``loss=None`` with a proxy
+    is the labels-only step: the heads write into the proxy's maps, no check stage and no photometric stage run, and
+    the ``ProxyResult`` is returned. ``loss`` and ``proxy`` must agree on ``uncertainty``."""
     if getattr(model, "precision", None) == "fp8":
         raise RuntimeError("adapt_step: precision='fp8' is the inference-only forward; adapt in fp32 or bf16")
+    if proxy is None:
+        if loss is None:
+            raise ValueError("adapt_step needs a loss, a proxy or both")
+    elif loss is not None and bool(loss.uncertainty) != bool(proxy.uncertainty):
+        raise ValueError(f"loss (uncertainty={loss.uncertainty}) and proxy (uncertainty={proxy.uncertainty}) must agree "
+                         "on uncertainty")
     eng = model.engine(inputs.device)
     n, _, H, W = (int(v) for v in inputs.shape)
+    if proxy is not None:
+        proxy._check_inputs(inputs)  # a frame no label fits into is refused before the forward
     with torch.cuda.device(eng.device):
         eng.pack_weights(train=True)
         eng.forward(inputs, train=True)
-        disp, logvar = loss.maps(n, H, W)
+        disp, logvar = (loss if loss is not None else proxy).maps(n, H, W)
         eng.heads(L.SD_HEADS_INFER, disp=disp, logvar=logvar)
-        res = loss.run(disp, logvar, inputs, count=eng.count)
+        if loss is not None:
+            res = loss.run(disp, logvar, inputs, count=eng.count)
+            if proxy is not None:
+                proxy.last = proxy.run(disp, logvar, inputs, into=res, count=eng.count)
+        else:
+            res = proxy.last = proxy.run(disp, logvar, inputs, count=eng.count)
         eng.heads(L.SD_HEADS_GRADS, gdisp=res.gdisp, glogvar=res.glogvar)
         eng.backward()
         optimizer.fused_step(gather_grads=False, gate_on_count=True)
     return res
 
 
-def adapt_epoch(model, loader, device, optimizer, loss: SelfSupLoss, log_every_batches: int | None = None, logger=None):
+def adapt_epoch(model, loader, device, optimizer, loss: SelfSupLoss | None, log_every_batches: int | None = None,
+                logger=None, proxy=None):
     """``adapt_step`` over the batches ``{"input": float32 [n, 6, H, W]}`` of ``loader`` (any other key is ignored: labels
     are not used). Returns the epoch's pixel-weighted means (``SelfSupLoss.means``: loss, photo, smooth,
     visible_fraction, grad_l1, steps; ssim when the loss has the term). The sums are read once per ``log_every_batches`` steps (``logger.log_metrics``,
-    as ``run_epoch``) and once at the end."""
+    as ``run_epoch``) and once at the end. With ``proxy`` (a ``proxy.ProxyLoss``) the means also carry its ``proxy_*``
+    keys (``ProxyLoss.means``); with ``loss=None`` they are the proxy's alone."""
     model.train(True)
-    loss._bind_device(torch.empty(0, device=device))
-    loss.reset()
-    since, step = None, 0
+    if loss is None and proxy is None:
+        raise ValueError("adapt_epoch needs a loss, a proxy or both")
+    stages = [s for s in (loss, proxy) if s is not None]
+    for s in stages:
+        s._bind_device(torch.empty(0, device=device))
+        s.reset()
+
+    def read(since):
+        """The stages' means merged (the loss's keys, then the proxy's ``proxy_*``), and their host totals."""
+        out, tot = None, []
+        for s, prev in zip(stages, since):
+            m = s.means(prev)
+            tot.append(s.last_totals)
+            if m is None:
+                continue
+            if s is proxy and loss is not None:
+                m = {k: v for k, v in m.items() if k.startswith("proxy_")}
+            out = m if out is None else {**out, **m}
+        return out, tot
+
+    since, step = [None] * len(stages), 0
     for batch in loader:
         step += 1
-        adapt_step(model, optimizer, batch["input"].to(device, non_blocking=True), loss)
+        adapt_step(model, optimizer, batch["input"].to(device, non_blocking=True), loss, proxy=proxy)
         if logger is not None and log_every_batches and step % log_every_batches == 0:
-            m = loss.means(since)
-            since = loss.last_totals
+            m, since = read(since)
             if m is not None:
                 logger.log_metrics({f"adapt_{k}_step": v for k, v in m.items() if v is not None}, step=step)
-    means = loss.means()
+    means, _ = read([None] * len(stages))
     if means is None:
         raise RuntimeError("No batches in this epoch.")
     return means
