@@ -8,7 +8,8 @@ _functional_tensor.py``: ``_blend``, ``rgb_to_grayscale``, ``adjust_brightness/c
 saturation/hue/gamma``, ``_rgb2hsv``, ``_hsv2rgb``, ``gaussian_blur`` with
 ``_get_gaussian_kernel2d`` and reflect padding). No reference test pins these ops: parity for
 the augmentation is "unpinned"  and rests on this restatement.
-Tensors are CHW float32 in [0, 1] on the CPU.
+Tensors are CHW float32 in [0, 1] on the CPU; float64 tensors run through the same code and
+give the float64 statement.
 """
 
 from __future__ import annotations
@@ -91,15 +92,15 @@ def adjust_gamma(img, gamma, gain=1.0):
     return (gain * img**gamma).clamp(0, 1)
 
 
-def _gaussian_kernel1d(kernel_size: int, sigma: float) -> torch.Tensor:
+def _gaussian_kernel1d(kernel_size: int, sigma: float, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     ksize_half = (kernel_size - 1) * 0.5
-    x = torch.linspace(-ksize_half, ksize_half, steps=kernel_size)
+    x = torch.linspace(-ksize_half, ksize_half, steps=kernel_size, dtype=dtype)
     pdf = torch.exp(-0.5 * (x / sigma).pow(2))
     return pdf / pdf.sum()
 
 
 def gaussian_blur(img, kernel_size: int, sigma: float):
-    k1 = _gaussian_kernel1d(kernel_size, sigma)
+    k1 = _gaussian_kernel1d(kernel_size, sigma, img.dtype)  # the image's type: float64 images give a float64 statement
     k2 = torch.mm(k1[:, None], k1[None, :])
     kernel = k2.expand(img.shape[-3], 1, kernel_size, kernel_size)
     pad = kernel_size // 2

@@ -473,7 +473,9 @@ __global__ void k_aug_blur_noise(const float* __restrict__ work, int H, int W, c
             }
         }
         if (std > 0.f) {
-            const float2 z = normal2_at(seed, ((uint64_t)plane * HW + px) >> 1);
+            // one counter per pixel pair of a plane, ceil(HW/2) per plane: for even HW this is (plane*HW + px) >> 1;
+            // that form gave the last pixel of an even plane and the first pair of the next one draw when HW is odd
+            const float2 z = normal2_at(seed, (uint64_t)plane * ((HW + 1) >> 1) + (px >> 1));
             v[0] += z.x * std;
             v[1] += z.y * std;
         }

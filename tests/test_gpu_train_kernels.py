@@ -1,6 +1,7 @@
 """The training step's small kernels through the C ABI against the float64 statements of tests/train_kernels_ref.py
 (needs an MI355X): the BatchNorm finalizes, reduces and apply (csrc/bn.hip), the fused heads + loss + gradient
-(csrc/heads.hip), AdamW and the valid count (csrc/misc.hip).
+(csrc/heads.hip), AdamW and the valid count (csrc/misc.hip), the MaxPool2d forward sd_bnrelu_pool (csrc/conv_fast.hip)
+and backward + skip add + fused BatchNorm-backward sums sd_pool_bwd_add (csrc/bn.hip).
 
 Tolerances (u = 2^-24; none is fitted to the kernels' output):
   exact     counts, step, scratch, num_batches_tracked, the single-rank bit identities, zeros the contract promises;
@@ -23,6 +24,14 @@ Tolerances (u = 2^-24; none is fitted to the kernels' output):
             reference: disp: s_d = sum |act*wd| + |bd|; logvar: s_l = sum |act*wl| + |bl|; a gradient or metric
             term g: |g| * (2 + s_d + s_l) (exp(-lv) turns lv's absolute error into a relative one), summed for the
             sums. Sums of such values add the `sums` bound.
+  pooling   the inputs sit on a 2^-6 grid whose windows an fp32 fma and float64 order alike
+            (train_kernels_ref.make_pool_inputs; the gap between a window's two largest values is 0 or above
+            8 * u * max|z|, asserted), so the winner is the reference's in every window: forward = the bf16 interval of
+            one fma rounding (u * |ref|); backward = dskip bit for bit off the arg-max (exactly 0 without dskip), one
+            fp32 add (u * |ref|) at it, exactly dpool without dskip; fused sums = the `sums` rule with n = 4 adds per
+            loop trip and m = 256/(C/8), evaluated on the da the kernel stored, + 3 roundings for dz*xhat.
+            tests/test_train_kernels_ref_cpu.py runs these checks on an fp32 emulation: a last-max tie-break, an
+            arg-max before the ReLU or on |scale| and a truncating store each fail them.
 
 Measured on an MI355X (every test prints its figures; run with -s): the fp32 CPU restatement's deviation from float64
 where the rule uses one (smallest .. largest over the cases with P >= 64), and the largest device deviation as a
@@ -50,6 +59,13 @@ bound) by construction (a value next to a rounding tie); their check is the inte
   heads_bnsum sum dz, sum dz*xhat        (from da's)              0.081, 0.081   (other outputs as sd_heads)
   count_valid                            -                        exact
   adamw p, m, v                          -                        0.19, 0.67, 0.59
+  bnrelu_pool (bf16)                     -                        interval met (1.0 of half a bf16 ulp), all bits pinned
+  pool_bwd_add da fp32 / bf16            -                        1.0 (an add that rounds by half an ulp of a power of
+                                                                  two) / interval met; without dskip: exact
+  pool_bwd_add sum dz, sum dz*xhat       (from the stored da)     fp32 0.17, 0.20; bf16 0.0026, 0.25
+  pool_bwd_add past one sweep (bf16)     -                        768 rows x 256 < 262144 items at (1,128,128,512):
+                                                                  da interval met; sums 0.00011, 0.0038
+  pool forward / backward winner         -                        interval met, all bits pinned
 """
 
 import math
@@ -743,3 +759,200 @@ def test_adamw(n, step0, wd):
     torch.cuda.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(before, (p, m, v)))
     assert int(step) == step0 + 5 and scratch.view(torch.int32).cpu().tolist() == [0, 0, 0, 0]
+
+
+# ------------------------------------------------------------------ 9. sd_bnrelu_pool, sd_pool_bwd_add
+# (1,2,2,8): one window, cpr = C/8 = 1; (2,6,10,24): cpr = 3 does not divide 256; (1,4,4,2048): cpr = 256, the largest C
+POOL_SHAPES = [(1, 2, 2, 8), (2, 6, 10, 24), (3, 8, 12, 32), (1, 4, 4, 2048), (2, 16, 20, 256)]
+POOL_FWD_LARGE = (5, 128, 128, 1024)  # B*(H/2)*(W/2)*(C/8) = 2621440 > 8192*256: the grid-stride loop runs again
+_POOL = {}
+
+
+def _pool_case(shape, prec):
+    key = (shape, prec)
+    if key not in _POOL:
+        inp = R.make_pool_inputs(*shape, DTYPES[prec], seed=sum(shape))
+        # the condition the ordering argument rests on (train_kernels_ref.make_pool_inputs)
+        assert inp["gap"] > 8 * U32 * inp["zmax"], (shape, inp["gap"], inp["zmax"])
+        _POOL[key] = inp
+    return _POOL[key]
+
+
+def _pool_large_case(shape):
+    """One sample from the builder; sample b is that sample rolled by b windows along W (the windows stay aligned, the
+    samples differ), so a large batch costs one sample's random draws. The references are still taken per sample."""
+    B, H, W, C = shape
+    one = R.make_pool_inputs(1, H, W, C, torch.bfloat16, seed=H + C)
+    assert one["gap"] > 8 * U32 * one["zmax"]
+    inp = dict(one)
+    for k, (h, w) in (("y", (H, W)), ("dskip", (H, W)), ("dpool", (H // 2, W // 2))):
+        v = one[k].view(h, w, C)
+        step = 2 if h == H else 1
+        inp[k] = torch.stack([torch.roll(v, step * b, 1) for b in range(B)]).reshape(B * h * w, C)
+    return inp
+
+
+def _sample(inp, b, H, W):
+    """Sample b of a batched pool input as a B = 1 input."""
+    n, n2 = H * W, (H // 2) * (W // 2)
+    out = dict(inp)
+    out.update(y=inp["y"][b * n:(b + 1) * n], dskip=inp["dskip"][b * n:(b + 1) * n], dpool=inp["dpool"][b * n2:(b + 1) * n2])
+    return out
+
+
+def _trunc_bf16(ref):
+    return (ref.float().view(torch.int32) & -65536).view(torch.float32).double()
+
+
+def check_pool_fwd(tag, got, inp, B, H, W, need_trunc_share=True):
+    """sd_bnrelu_pool's output (CPU tensor [B*(H/2)*(W/2)][C]) against the float64 statement: the fp32 value has one
+    fma rounding (tol32 = u*|ref|), nothing is allowed for the store. Pure CPU logic (also run on mutants by
+    test_train_kernels_ref_cpu.py)."""
+    ref = R.bnrelu_pool_ref(inp["y"], inp["scale"], inp["shift"], B, H, W).reshape(got.shape)
+    tol = U32 * ref.abs()
+    _check_bf16(tag, got, ref, tol)
+    if need_trunc_share:  # the check tells round-to-nearest from truncation
+        lo, hi = R.bf16_store_interval(ref, tol)
+        t = _trunc_bf16(ref)
+        assert float(((t < lo) | (t > hi)).double().mean()) > 0.25, tag
+
+
+def check_pool_bwd(tag, da, inp, B, H, W, prec, skip):
+    """sd_pool_bwd_add's da (CPU tensor [B*H*W][C] in the storage type) against ``pool_bwd_ref``.
+    Off the arg-max: da == dskip bit for bit (exactly 0 without dskip). At the arg-max: one fp32 add, tol = u*|ref|
+    (bf16: the round-to-nearest-even of such a value); without dskip exactly dpool. Pure CPU logic."""
+    ref, am = R.pool_bwd_ref(inp["y"], inp["scale"], inp["shift"], inp["dskip"] if skip else None, inp["dpool"], B, H, W)
+    ref = ref.reshape(da.shape)
+    hit = R.pool_hit(am, B, H, W).reshape(da.shape)
+    assert not bool(torch.isnan(da.float()).any()), tag
+    if not skip:
+        print(f"RATIO {tag} exact")
+        assert torch.equal(da.double(), ref), (tag, int((da.double() != ref).sum()))
+        return
+    bits = torch.int32 if prec == "fp32" else torch.int16
+    off_bad = (da.view(bits) != inp["dskip"].view(bits)) & ~hit
+    assert not bool(off_bad.any()), (tag, "off the arg-max", int(off_bad.sum()))
+    tol = torch.where(hit, U32 * ref.abs(), torch.zeros((), dtype=torch.float64))
+    if prec == "fp32":
+        _check(tag, da, ref, tol)
+    else:
+        _check_bf16(tag, da, ref, tol)
+
+
+def _pool_dev(inp):
+    return {k: v.to(DEV).contiguous() for k, v in inp.items() if torch.is_tensor(v)}
+
+
+def _run_pool_fwd(d, B, H, W, C):
+    out = torch.full((B * (H // 2) * (W // 2), C), float("nan"), dtype=torch.bfloat16, device=DEV)
+    L().call("sd_bnrelu_pool", L().SD_BF16, _d(d["y"]), _d(d["scale"]), _d(d["shift"]), B, H, W, C, _d(out),
+             L().stream_handle())
+    torch.cuda.synchronize()
+    return out.cpu()
+
+
+def _run_pool_bwd(d, B, H, W, C, prec, skip, fused):
+    lib = L()
+    rows = lib.call("sd_pool_bwd_rows", B, H, W, C)
+    da = torch.full((B * H * W, C), float("nan"), dtype=DTYPES[prec], device=DEV)
+    part = torch.full((rows, C, 2), float("nan"), device=DEV) if fused else None
+    lib.call("sd_pool_bwd_add", _sd(prec), _d(d["y"]), _d(d["scale"]), _d(d["shift"]), _d(d["dskip"]) if skip else None,
+             _d(d["dpool"]), B, H, W, C, _d(da), _d(d["mean"]) if fused else None, _d(d["invstd"]) if fused else None,
+             _d(part), lib.stream_handle())
+    torch.cuda.synchronize()
+    return da.cpu(), (part.double().sum(0).cpu() if fused else None), rows
+
+
+def _check_pool_sums(tag, got, sums, rows, total, C):
+    """partials summed over rows against bn_bwd_sums of the da the kernel stored: the `sums` rule with n = 4 adds per
+    loop trip of a thread (one per window position) and m = 256/cpr adds of the in-block reduction; sum dz*xhat has
+    k = 3 more roundings per term ((y - mean), * invstd, the product)."""
+    s1, s2, a1, a2 = sums
+    n, m = 4 * -(-total // (rows * 256)), 256 // (C // 8)
+    _check(f"{tag}.sum_dz", got[:, 0], s1, (n + m + 2) * U32 * a1)
+    _check(f"{tag}.sum_dz_xhat", got[:, 1], s2, (n + m + 2 + 3) * U32 * a2)
+
+
+@pytest.mark.parametrize("shape", POOL_SHAPES)
+def test_bnrelu_pool(shape):
+    B, H, W, C = shape
+    inp = _pool_case(shape, "bf16")
+    got = _run_pool_fwd(_pool_dev(inp), B, H, W, C)
+    check_pool_fwd(f"bnrelu_pool{list(shape)}", got, inp, B, H, W, need_trunc_share=got.numel() >= 1000)
+
+
+def test_bnrelu_pool_past_one_grid_sweep():
+    B, H, W, C = POOL_FWD_LARGE
+    assert B * (H // 2) * (W // 2) * (C // 8) > 8192 * 256
+    inp = _pool_large_case(POOL_FWD_LARGE)
+    got = _run_pool_fwd(_pool_dev(inp), B, H, W, C)
+    n2 = (H // 2) * (W // 2)
+    for b in range(B):  # the float64 reference sample by sample
+        check_pool_fwd(f"bnrelu_pool{list(POOL_FWD_LARGE)}@{b}", got[b * n2:(b + 1) * n2], _sample(inp, b, H, W), 1, H, W)
+
+
+@pytest.mark.parametrize("fused", [False, True])
+@pytest.mark.parametrize("skip", [True, False])
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+@pytest.mark.parametrize("shape", POOL_SHAPES)
+def test_pool_bwd_add(shape, prec, skip, fused):
+    B, H, W, C = shape
+    inp = _pool_case(shape, prec)
+    tag = f"pool_bwd{list(shape)}[{prec},{'skip' if skip else 'noskip'},{'fused' if fused else 'plain'}]"
+    d = _pool_dev(inp)
+    if fused and 256 % (C // 8):
+        # C/8 = 3 does not divide 256: the fused request is an error and nothing is launched
+        lib = L()
+        da = torch.full((B * H * W, C), float("nan"), dtype=DTYPES[prec], device=DEV)
+        part = torch.full((lib.call("sd_pool_bwd_rows", B, H, W, C), C, 2), float("nan"), device=DEV)
+        with pytest.raises(lib.StereoHipError, match="C/8 dividing 256"):
+            lib.call("sd_pool_bwd_add", _sd(prec), _d(d["y"]), _d(d["scale"]), _d(d["shift"]), _d(d["dskip"]),
+                     _d(d["dpool"]), B, H, W, C, _d(da), _d(d["mean"]), _d(d["invstd"]), _d(part), lib.stream_handle())
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(da.float()).all()) and bool(torch.isnan(part).all())
+        return
+    da, got, rows = _run_pool_bwd(d, B, H, W, C, prec, skip, fused)
+    check_pool_bwd(tag, da, inp, B, H, W, prec, skip)
+    if fused:
+        sums = R.bn_bwd_sums(da, inp["y"], inp["scale"], inp["shift"], inp["mean"], inp["invstd"])
+        _check_pool_sums(tag, got, sums, rows, B * (H // 2) * (W // 2) * (C // 8), C)
+
+
+def test_pool_bwd_add_past_one_grid_sweep():
+    """bf16, with dskip and the fused sums, at the smallest batch of 128 x 128 x 512 samples whose work exceeds the
+    resident-block cap (a runtime query), so every thread's loop runs more than once."""
+    lib = L()
+    H, W, C = 128, 128, 512
+    per = (H // 2) * (W // 2) * (C // 8)
+    B = next((b for b in (1, 2, 3, 4, 6, 8) if lib.call("sd_pool_bwd_rows", b, H, W, C) * 256 < b * per), None)
+    assert B is not None
+    rows = lib.call("sd_pool_bwd_rows", B, H, W, C)
+    assert rows * 256 < B * per
+    print(f"pool_bwd large case: B={B} rows={rows}")
+    inp = _pool_large_case((B, H, W, C))
+    da, got, rows2 = _run_pool_bwd(_pool_dev(inp), B, H, W, C, "bf16", True, True)
+    assert rows2 == rows
+    n = H * W
+    sums = None
+    for b in range(B):  # the float64 reference sample by sample
+        one = _sample(inp, b, H, W)
+        check_pool_bwd(f"pool_bwd[{B},{H},{W},{C}]@{b}", da[b * n:(b + 1) * n], one, 1, H, W, "bf16", True)
+        s = R.bn_bwd_sums(da[b * n:(b + 1) * n], one["y"], inp["scale"], inp["shift"], inp["mean"], inp["invstd"])
+        sums = s if sums is None else tuple(a + c for a, c in zip(sums, s))
+    _check_pool_sums(f"pool_bwd[{B},{H},{W},{C}]", got, sums, rows, B * per, C)
+
+
+@pytest.mark.parametrize("shape", POOL_SHAPES)
+def test_pool_forward_and_backward_agree_on_the_winner(shape):
+    """bf16: relu(fma(y, scale, shift)) at the position where sd_pool_bwd_add put dpool, rounded to bf16, is the element
+    sd_bnrelu_pool stored (dpool is nowhere 0 and dskip absent, so da != 0 marks the position)."""
+    B, H, W, C = shape
+    inp = _pool_case(shape, "bf16")
+    d = _pool_dev(inp)
+    da, _, _ = _run_pool_bwd(d, B, H, W, C, "bf16", False, False)
+    fwd = _run_pool_fwd(d, B, H, W, C)
+    put = R.pool_windows(da.double() != 0, B, H, W)
+    assert torch.equal(put.sum(3), torch.ones_like(put.sum(3)))  # one position per window and channel
+    z = R.pool_windows(torch.relu(inp["y"].double() * inp["scale"].double() + inp["shift"].double()), B, H, W)
+    at = (z * put).sum(3).reshape(fwd.shape)
+    _check_bf16(f"pool_winner{list(shape)}", fwd, at, U32 * at.abs())

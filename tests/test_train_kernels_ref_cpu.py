@@ -228,3 +228,139 @@ def test_adamw_restatement_matches_torch_optim(wd, step0):
     tp, tm, tv = R.adamw_tolerances(pf, grad, mf, vf, t, lr, wd, b1, b2, eps)
     assert bool(((p1.double() - pr).abs() <= tp).all()) and bool(((m1.double() - mr).abs() <= tm).all())
     assert bool(((v1.double() - vr).abs() <= tv).all())
+
+
+# ------------------------------------------------------------------ MaxPool2d(2) of relu(bn(y)): forward, backward
+def _pool_autograd(y, scale, shift, dpool, B, H, W):
+    """F.max_pool2d on relu(scale*y + shift) in float64 (NCHW) and its backward: (pooled, grad), both NHWC."""
+    C = y.shape[-1]
+    a = torch.relu(y.double() * scale.double() + shift.double()).reshape(B, H, W, C)
+    x = a.permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    p = torch.nn.functional.max_pool2d(x, 2)
+    p.backward(dpool.double().reshape(B, H // 2, W // 2, C).permute(0, 3, 1, 2))
+    return p.detach().permute(0, 2, 3, 1), x.grad.permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("B,H,W,C", [(1, 2, 2, 8), (2, 6, 10, 24), (3, 8, 12, 32)])
+def test_pool_references_reproduce_max_pool2d_autograd_on_tie_free_inputs(B, H, W, C):
+    g = torch.Generator().manual_seed(H * W)
+    y = torch.randn(B * H * W, C, generator=g, dtype=torch.float64) + 0.8  # fine-grained and mostly positive: no ties
+    scale = torch.rand(C, generator=g, dtype=torch.float64) + 0.5
+    scale[::3] *= -1
+    shift = torch.randn(C, generator=g, dtype=torch.float64) * 0.3
+    dskip = torch.randn(B * H * W, C, generator=g, dtype=torch.float64)
+    dpool = torch.randn(B * (H // 2) * (W // 2), C, generator=g, dtype=torch.float64)
+    a = R.pool_windows(torch.relu(y * scale + shift), B, H, W)
+    top = a.topk(2, dim=3).values
+    keep = top[:, :, :, 0] > top[:, :, :, 1]  # tie-free windows (all-zero windows of the negative channels are ties)
+    assert float(keep.double().mean()) > 0.5
+    pooled, grad = _pool_autograd(y, scale, shift, dpool, B, H, W)
+    assert torch.equal(R.bnrelu_pool_ref(y, scale, shift, B, H, W), pooled)
+    full = R.pool_unwindows(keep.unsqueeze(3).expand(-1, -1, -1, 4, -1), B, H, W)
+    for skip in (dskip, None):
+        da, am = R.pool_bwd_ref(y, scale, shift, skip, dpool, B, H, W)
+        want = grad + (0 if skip is None else skip.reshape(B, H, W, C))
+        assert torch.equal(da[full], want[full])
+        assert torch.equal(R.pool_hit(am, B, H, W)[full], (grad != 0)[full])
+    assert torch.equal(R.pool_unwindows(R.pool_windows(y, B, H, W), B, H, W).reshape(-1, C), y)
+
+
+def test_pool_reference_first_max_on_the_planted_ties():
+    """The planted cases of test_gpu_ops.test_pool_bwd_first_max_tie_break_and_skip_add: y = 0 except one 5 at window
+    position 1 and one -3; scale 1, shift 0. The numpy statement (first maximum) picks position 1 in the window with
+    the 5 and position 0 in every other window-channel, all of which are four-way ties at 0 after the ReLU. ATen's
+    float64 CPU max_pool2d backward makes the same choice here (checked below), so the two agree on these ties too;
+    the numpy statement remains the contract."""
+    B, H, W, C = 1, 4, 4, 8
+    y = torch.zeros(B, H, W, C, dtype=torch.float64)
+    y[0, 0, 1, 0] = 5.0
+    y[0, 2, 2, 1] = -3.0
+    dpool = torch.arange(B * 2 * 2 * C, dtype=torch.float64) + 1
+    one, zero = torch.ones(C), torch.zeros(C)
+    da, am = R.pool_bwd_ref(y.reshape(-1, C), one, zero, None, dpool.reshape(-1, C), B, H, W)
+    want = torch.zeros(B, 2, 2, C, dtype=torch.int64)
+    want[0, 0, 0, 0] = 1
+    assert torch.equal(am, want)
+    _, grad = _pool_autograd(y.reshape(-1, C), one, zero, dpool.reshape(-1, C), B, H, W)
+    assert torch.equal(da, grad)
+
+
+POOL_SHAPES = [(1, 2, 2, 8), (2, 6, 10, 24), (3, 8, 12, 32), (1, 4, 4, 2048), (2, 16, 20, 256), (1, 128, 128, 512)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("shape", POOL_SHAPES)
+def test_pool_input_builder_keeps_its_promises(shape, dtype):
+    """y on the 2^-6 grid in [-4, 4] and exact in the storage type; |scale| in [0.5, 1.5], every third negative; the
+    gap between the two largest relu(z) of a window is 0 or far above an fp32 rounding; with 1000 window-channels
+    or more, at least 5 % tie exactly for a positive maximum and at least 5 % are all zero after the ReLU."""
+    B, H, W, C = shape
+    inp = R.make_pool_inputs(B, H, W, C, dtype, seed=sum(shape))
+    k = inp["y"].double() * 64
+    assert torch.equal(k, k.round()) and float(k.abs().max()) <= 256
+    s = inp["scale"]
+    assert bool((s[::3] < 0).all()) and bool((s.abs() >= 0.5).all()) and bool((s.abs() <= 1.5).all())
+    assert int((s > 0).sum()) == C - len(s[::3])
+    assert inp["scale"].dtype == inp["shift"].dtype == torch.float32
+    assert inp["gap"] > 8 * R.U32 * inp["zmax"]
+    assert inp["gap"] >= 0.5 * 2.0 ** -7 * (1 - 1e-6)  # |scale| * 2^-7 at the least
+    assert not bool((inp["dpool"] == 0).any())
+    ties, zeros = R.pool_tie_shares(inp["y"], s, inp["shift"], B, H, W)
+    print(f"pool builder {shape} {dtype}: ties {ties:.3f} all-zero {zeros:.3f} gap {inp['gap']:.3g}")
+    if B * (H // 2) * (W // 2) * C >= 1000:
+        assert ties >= 0.05 and zeros >= 0.05
+    # the ordering argument, checked directly: an fp32 fma (the float64 value rounded once) orders every window alike
+    z64 = inp["y"].double() * s.double() + inp["shift"].double()
+    a32 = R.pool_windows(torch.relu(z64.float()), B, H, W)
+    a64 = R.pool_windows(torch.relu(z64), B, H, W)
+    assert torch.equal(torch.from_numpy(np.argmax(a32.numpy(), 3)), torch.from_numpy(np.argmax(a64.numpy(), 3)))
+    assert torch.equal(a32 == a32.max(3, keepdim=True).values, a64 == a64.max(3, keepdim=True).values)
+
+
+def _emulated_pool(inp, B, H, W, dtype, skip, variant="ok"):
+    """What a kernel computes, in fp32 on the CPU: z by one rounding of the exact fma, the arg-max of relu(z) (first
+    maximum), one fp32 add, a round-to-nearest-even store; `variant` swaps in one defect. Returns (pooled, da)."""
+    scale = inp["scale"].abs() if variant == "abs_scale" else inp["scale"]
+    z = (inp["y"].double() * scale.double() + inp["shift"].double()).float()
+    a = R.pool_windows(z if variant == "pre_relu" else torch.relu(z), B, H, W).numpy()
+    am = 3 - np.argmax(a[:, :, :, ::-1], 3) if variant == "last_max" else np.argmax(a, 3)
+    hit = R.pool_hit(torch.from_numpy(am.copy()), B, H, W).reshape(inp["y"].shape)
+    C = inp["y"].shape[1]
+    dp = R.pool_unwindows(inp["dpool"].float().reshape(B, H // 2, W // 2, 1, C).expand(-1, -1, -1, 4, -1), B, H, W)
+    o = (inp["dskip"].float() if skip else torch.zeros(inp["y"].shape)) + torch.where(hit, dp.reshape(hit.shape),
+                                                                                      torch.zeros(()))
+    pooled = R.pool_windows(torch.relu(z), B, H, W).max(3).values.reshape(-1, C)
+    if variant == "trunc":
+        cut = lambda t: (t.view(torch.int32) & -65536).view(torch.float32).to(dtype)  # noqa: E731
+        return cut(pooled.contiguous()), cut(o.contiguous())
+    return pooled.to(torch.bfloat16), o.to(dtype)
+
+
+@pytest.mark.parametrize("shape", [(2, 6, 10, 24), (3, 8, 12, 32)])
+def test_pool_checks_pass_a_correct_kernel_and_fail_each_defect(shape):
+    """The GPU tests' own check functions, run here on an fp32 emulation of the kernels: the faithful one passes every
+    check; a last-max tie-break, an arg-max taken before the ReLU or on |scale|, and a truncating bf16 store fail."""
+    from test_gpu_train_kernels import check_pool_bwd, check_pool_fwd
+
+    B, H, W, C = shape
+    for prec, dtype in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        inp = R.make_pool_inputs(B, H, W, C, dtype, seed=sum(shape))
+        for skip in (True, False):
+            pooled, da = _emulated_pool(inp, B, H, W, dtype, skip)
+            check_pool_bwd("emulated", da, inp, B, H, W, prec, skip)
+            for variant in ("last_max", "pre_relu", "abs_scale"):
+                _, bad = _emulated_pool(inp, B, H, W, dtype, skip, variant)
+                with pytest.raises(AssertionError):
+                    check_pool_bwd(variant, bad, inp, B, H, W, prec, skip)
+        if prec == "bf16":
+            check_pool_fwd("emulated", pooled, inp, B, H, W, need_trunc_share=False)
+            tp, tda = _emulated_pool(inp, B, H, W, dtype, True, "trunc")
+            with pytest.raises(AssertionError):
+                check_pool_fwd("trunc", tp, inp, B, H, W, need_trunc_share=False)
+            with pytest.raises(AssertionError):
+                check_pool_bwd("trunc", tda, inp, B, H, W, prec, True)
+            _, absd = _emulated_pool(inp, B, H, W, dtype, True, "abs_scale")
+            pa = R.pool_windows(torch.relu((inp["y"].double() * inp["scale"].abs().double()
+                                            + inp["shift"].double()).float()), B, H, W).max(3).values.reshape(-1, C)
+            with pytest.raises(AssertionError):
+                check_pool_fwd("abs_scale", pa.to(torch.bfloat16), inp, B, H, W, need_trunc_share=False)

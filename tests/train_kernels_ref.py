@@ -1,5 +1,6 @@
 """Float64 references and input builders for the training step's small kernels: the BatchNorm finalizes, reduces and
-apply (csrc/bn.hip), the fused heads + loss + gradient (csrc/heads.hip), AdamW and the valid count (csrc/misc.hip).
+apply (csrc/bn.hip), the fused heads + loss + gradient (csrc/heads.hip), AdamW and the valid count (csrc/misc.hip),
+the MaxPool2d forward (csrc/conv_fast.hip) and backward + skip add (csrc/bn.hip).
 
 Everything here is NumPy / torch on the CPU and imports nothing from the package. Each operation is stated from the
 contract in include/stereo_hip.h and the lines of the reference model it cites; tests/test_train_kernels_ref_cpu.py
@@ -410,3 +411,97 @@ def adamw_tolerances(p0, g, m0, v0, t, lr, wd, b1, b2, eps):
     denom = torch.sqrt(v) / bc2s + eps
     tol_p = 20 * U32 * ((p0 * decay).abs() + step_size * tm / denom)
     return tol_p, tol_m, tol_v
+
+
+# ------------------------------------------------------------------ MaxPool2d(2) of relu(bn(y)) (model.py:59,83-86)
+def pool_windows(x, B, H, W):
+    """NHWC rows [B*H*W][C] (or [B][H][W][C]) -> [B][H/2][W/2][4][C], window position k = 2*dy + dx."""
+    C = x.shape[-1]
+    return x.reshape(B, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H // 2, W // 2, 4, C)
+
+
+def pool_unwindows(xw, B, H, W):
+    """The inverse of ``pool_windows``: [B][H/2][W/2][4][C] -> [B][H][W][C]."""
+    C = xw.shape[-1]
+    return xw.reshape(B, H // 2, W // 2, 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
+
+
+def bnrelu_pool_ref(y, scale, shift, B, H, W):
+    """sd_bnrelu_pool: max over each 2x2 window of relu(scale*y + shift), float64, [B][H/2][W/2][C]."""
+    a = torch.relu(f64(y) * f64(scale) + f64(shift))
+    return pool_windows(a, B, H, W).max(3).values
+
+
+def pool_bwd_ref(y, scale, shift, dskip, dpool, B, H, W):
+    """sd_pool_bwd_add: da = dskip (0 when absent) + dpool at the arg-max of relu(scale*y + shift) over each 2x2
+    window, the FIRST maximum in window order k = 2*dy + dx (numpy.argmax documents first occurrence).
+    Returns (da [B][H][W][C] float64, argmax [B][H/2][W/2][C] int64)."""
+    a = pool_windows(torch.relu(f64(y) * f64(scale) + f64(shift)), B, H, W)
+    am = torch.from_numpy(np.argmax(a.numpy(), axis=3))
+    hit = torch.arange(4).view(1, 1, 1, 4, 1) == am.unsqueeze(3)
+    C = a.shape[-1]
+    g = torch.where(hit, f64(dpool).reshape(B, H // 2, W // 2, 1, C), torch.zeros((), dtype=torch.float64))
+    da = pool_unwindows(g, B, H, W)
+    if dskip is not None:
+        da = da + f64(dskip).reshape(B, H, W, C)
+    return da, am
+
+
+def pool_hit(am, B, H, W):
+    """[B][H][W][C] bool: the positions ``pool_bwd_ref``'s arg-max selects."""
+    return pool_unwindows(torch.arange(4).view(1, 1, 1, 4, 1) == am.unsqueeze(3), B, H, W)
+
+
+def pool_top2_gap(y, scale, shift, B, H, W):
+    """(smallest non-zero gap between the two largest relu(z) of any window, max |z|), z = scale*y + shift in float64."""
+    z = f64(y) * f64(scale) + f64(shift)
+    top = pool_windows(torch.relu(z), B, H, W).topk(2, dim=3).values
+    gap = top[:, :, :, 0] - top[:, :, :, 1]
+    nz = gap[gap > 0]
+    return (float(nz.min()) if nz.numel() else math.inf), float(z.abs().max())
+
+
+def pool_tie_shares(y, scale, shift, B, H, W):
+    """Shares of window-channels with (an exact tie for a positive maximum, all four values zero after the ReLU)."""
+    a = pool_windows(torch.relu(f64(y) * f64(scale) + f64(shift)), B, H, W)
+    mx = a.max(3, keepdim=True).values
+    ties = ((a == mx).sum(3) >= 2) & (mx.squeeze(3) > 0)
+    return float(ties.double().mean()), float((mx == 0).double().mean())
+
+
+def make_pool_inputs(B, H, W, C, dtype, seed):
+    """Inputs of the pooling kernels, NHWC rows: y, dskip [B*H*W][C] and dpool [B*(H/2)*(W/2)][C] in the storage type,
+    fp32 scale, shift, mean, invstd [C], and the (gap, max |z|) of ``pool_top2_gap``.
+    y lies on a coarse grid, multiples of 2^-6 in [-4, 4] (exact in bf16: at most 8 significant bits), so exact ties
+    inside a window are common; they are made commoner still: in about a third of the window-channels one position
+    repeats another, and about 6 % of them are pushed to the non-positive side of their channel (all zero after the
+    ReLU). |scale| is in [0.5, 1.5], every third channel negative. shift is about 0.3*N(0,1), placed half-way between
+    two grid points of its channel: shift = scale*(m + 0.5)*2^-6 for an integer m, so no z = scale*y + shift is
+    closer to 0 than |scale|*2^-7, and two unequal z of one channel differ by at least |scale|*2^-6: far above an
+    fp32 rounding of z (2^-24 * 7), so an fp32 fma and float64 order every window the same way (the argument of
+    ``relu_mask``). No window has to be left out of a comparison."""
+    g = torch.Generator().manual_seed(seed)
+    H2, W2 = H // 2, W // 2
+    scale = torch.rand(C, generator=g) + 0.5
+    scale[::3] *= -1
+    m = torch.round(torch.randn(C, generator=g) * 0.3 * 64.0 / scale - 0.5)
+    shift = (scale * ((m + 0.5) / 64.0)).float()
+    k = torch.randint(-256, 257, (B, H2, W2, 4, C), generator=g, dtype=torch.int16)
+    r = torch.rand(B, H2, W2, 1, C, generator=g)
+    # one position repeats another (positions 0..3 in turn, by the same draw)
+    src, dst = (r * 64).long() % 4, (r * 256).long() % 4
+    copy = (r < 1.0 / 3.0) & (src != dst)
+    k = torch.where(copy & (torch.arange(4).view(1, 1, 1, 4, 1) == dst), k.gather(3, src), k)
+    # all four on the non-positive side: z = -|scale| * (|k| + 64) / 64 + shift
+    neg = r > 0.94
+    side = -torch.sign(scale).to(torch.int16)
+    k = torch.where(neg, side * (k.abs() + 64).clamp_max(256), k)
+    y = store(pool_unwindows(k, B, H, W).reshape(B * H * W, C).float() / 64.0, dtype)
+    dskip = store(torch.randn(B * H * W, C, generator=g), dtype)
+    dpool = store(torch.randn(B * H2 * W2, C, generator=g), dtype)
+    dpool[dpool == 0] = 1.0  # a zero gradient would hide where the kernel put it
+    mean = torch.randn(C, generator=g) * 0.2
+    invstd = torch.rand(C, generator=g) + 0.5
+    gap = pool_top2_gap(y, scale, shift, B, H, W)
+    return {"y": y, "scale": scale, "shift": shift, "dskip": dskip, "dpool": dpool, "mean": mean, "invstd": invstd,
+            "gap": gap[0], "zmax": gap[1]}
