@@ -2,6 +2,8 @@
 
 fp32 mode (exact-f32 MFMA): max |Δ| <= 1e-4 * (1 + max|ref|).  bf16 mode: inputs are first
 rounded to bf16 on both sides; tolerance 2e-2 relative to max|ref| (bf16 output rounding + K-sum order).
+The conv, ConvTranspose and weight-gradient kernels are also pinned bit for bit against float64 on lattice inputs, with
+no tolerance, in tests/test_gpu_conv_exact.py (reference: tests/conv_lattice_ref.py).
 """
 
 import numpy as np
