@@ -619,6 +619,36 @@ int sd_sgm_post_n(int n, const int16_t* q, int H, int W, const double* Qdev, flo
 /* sd_sgm_center per stream: z f32 [n][H][W] -> out f32 [n], one block per stream. */
 int sd_sgm_center_n(int n, const float* z, int H, int W, int window, float* out, sd_stream s);
 
+/* ---- the census / Hamming pixel cost of the matcher ("The census cost": steps 2c and 3c) ----
+ * In place of the prefilter and the Birchfield-Tomasi cost: a descriptor per pixel of each gray plane that depends only
+ * on the order of the intensities inside that image, and the Hamming distance of two descriptors as the pixel cost.
+ * Everything from the block sum on is the matcher's as above. Windows (rows x columns): 3x3, 5x5, 7x7, 7x9;
+ * nbits = rows * columns - 1 = 8, 24, 48, 62. The uint16 bound is npaths * (block_size^2 * nbits + P2) <= 65535, else
+ * SD_EINVAL; pre_filter_cap is checked as before and otherwise unused. Pinned bit for bit to tests/sgm_census_ref.py. */
+#define SD_SGM_COST_BT 0
+#define SD_SGM_COST_CENSUS 1
+/* gray u8 [n][H][W] -> desc u64 [n][H][W] (8-B aligned). Bit k of a descriptor: the k-th position of the win_h x win_w
+ * window around the pixel, row-major (dy outer from -win_h/2, dx inner from -win_w/2) with the centre skipped, holds a
+ * value strictly below the centre's; positions outside [0, H) x [0, W) of the pixel's own image take the nearest pixel
+ * of it (never another stream's). Bits >= nbits are zero. Any other window: SD_EINVAL. */
+int sd_sgm_census_n(int n, const uint8_t* gray, int H, int W, int win_h, int win_w, uint64_t* desc, sd_stream s);
+/* sd_sgm_cost with the pixel cost popcount(desc_l[y][x] ^ desc_r[y][x - d - min_disparity]) (0..nbits) in place of
+ * Birchfield-Tomasi; C, tmp and the block sum as there. nbits: 8, 24, 48 or 62. */
+int sd_sgm_cost_census(const uint64_t* desc_l, const uint64_t* desc_r, int H, int W, int min_disparity,
+                       int num_disparities, int block_size, int nbits, uint16_t* C, uint16_t* tmp, sd_stream s);
+/* The workspace of sd_sgm_compute_cost_n. SD_SGM_COST_BT: sd_sgm_ws_bytes_n. SD_SGM_COST_CENSUS: every stream's slice is
+ * sd_sgm_ws_bytes followed by two descriptor planes of a(8 H W) bytes, so the Birchfield-Tomasi layout is a prefix of
+ * it (the prefiltered planes stay unwritten). Negative for n outside 1..64 or an unknown cost. Host only. */
+long long sd_sgm_ws_bytes_cost_n(int n, int H, int W, int D, int cost);
+/* sd_sgm_compute_n with a choice of pixel cost. SD_SGM_COST_BT ignores the window and issues exactly
+ * sd_sgm_compute_n's launches on its workspace; SD_SGM_COST_CENSUS runs sd_sgm_census_n on both sides and
+ * sd_sgm_cost_census in place of the two prefilter launches and sd_sgm_cost. work: sd_sgm_ws_bytes_cost_n, 256-B
+ * aligned. */
+int sd_sgm_compute_cost_n(int n, const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
+                          int num_disparities, int block_size, int P1, int P2, int disp12_max_diff,
+                          int uniqueness_ratio, int speckle_window, int speckle_range, int pre_filter_cap, int mode,
+                          int cost, int win_h, int win_w, void* work, int16_t* q, sd_stream s);
+
 /* ---- per-epoch preview montages of the training CLI (eval_utils.py:42-73: _normalize_map, save_preview_montage) ----
  * One sample: left | right | gray(target) | gray(pred) along the width, uint8 RGB; each map normalised to the 5th-95th
  * percentile of its own finite values. Two steps: the percentiles (an exact select, on the device), then the bytes.

@@ -23,6 +23,7 @@ SD_EPI_STORE, SD_EPI_STATS, SD_EPI_SPLIT, SD_EPI_PIXSHUF, SD_EPI_SPLIT_STATS = 0
 SD_W_CONV3, SD_W_CONVT, SD_W_ROWSUM = 0, 1, 2
 SD_HEADS_INFER, SD_HEADS_LOSS, SD_HEADS_GRADS = 0, 1, 2
 SD_SGM_MODE_SGBM, SD_SGM_MODE_HH, SD_SGM_MODE_3WAY, SD_SGM_MODE_HH4 = 0, 1, 2, 3  # cv2.StereoSGBM's constants
+SD_SGM_COST_BT, SD_SGM_COST_CENSUS = 0, 1
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -221,6 +222,11 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_sgm_speckle_n": (_i, [_i, _p, _i, _i, _i, _i, _i, _p, _p]),
     "sd_sgm_post_n": (_i, [_i, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "sd_sgm_center_n": (_i, [_i, _p, _i, _i, _i, _p, _p]),
+    # the census / Hamming pixel cost of the matcher
+    "sd_sgm_census_n": (_i, [_i, _p, _i, _i, _i, _i, _p, _p]),
+    "sd_sgm_cost_census": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "sd_sgm_ws_bytes_cost_n": (ctypes.c_longlong, [_i, _i, _i, _i, _i]),
+    "sd_sgm_compute_cost_n": (_i, [_i, _p, _p] + [_i] * 16 + [_p, _p, _p]),
     # the epoch preview montages
     "sd_quantile_select_ws_bytes": (ctypes.c_longlong, [_i]),
     "sd_quantile_select_n": (_i, [_i, _p, _i, _d, _d, _p, _p, _p]),
@@ -290,7 +296,7 @@ def kernel_name(name: str, *args) -> str:
 def call(name: str, *args) -> int:
     """Call an int-returning entry point; raise StereoHipError with sd_last_error() on failure."""
     lib = load()
-    if name.endswith(("_rows", "_splits", "_ok", "_bytes", "_bytes_n")) or name == "sd_version":
+    if name.endswith(("_rows", "_splits", "_ok", "_bytes", "_bytes_n", "_bytes_cost_n")) or name == "sd_version":
         return getattr(lib, name)(*args)
     if _hook is not None:
         _hook(name, args, "pre")

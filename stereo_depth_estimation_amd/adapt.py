@@ -5,7 +5,8 @@
         [--height H --width W] [--epochs 1] [--batch-size 16] [--lr 1e-5] [--weight-decay 0] [--precision fp32|bf16] \\
         [--w-smooth 0.1] [--edge-gamma 10] [--occ-tol 0.5] [--no-uncertainty] [--max-samples 0] [--seed 42] \\
         [--base-channels 32] [--read-threads 16] [--device cuda] [--ssim-weight 0] \\
-        [--proxy-weight 0] [--proxy-only] [--proxy-num-disparities 64] [--proxy-block-size 5] [--proxy-mode 3way]
+        [--proxy-weight 0] [--proxy-only] [--proxy-num-disparities 64] [--proxy-block-size 5] [--proxy-mode 3way] \\
+        [--proxy-cost bt|census] [--proxy-census-window 7x9]
 
 Runs ``selfsup.adapt_epoch`` over the pairs: the photometric + smoothness objective of ``sd_selfsup_loss`` (selfsup.py,
 INTEGRATION.md "sd_selfsup_loss") through the model's training forward, the hand-scheduled backward and AdamW. The frames
@@ -31,6 +32,13 @@ stage, no photometric stage). ``--proxy-num-disparities`` (64), ``--proxy-block-
 are the matcher's; they are parameters, not measured optima. The batch size is then at most 64 (the matcher's streams)
 and the width must exceed the disparity range. With W > 0 the meta gains the proxy arguments, the epochs ``proxy_loss``,
 ``proxy_mae`` and ``proxy_fraction``, and the meta ``proxy_mae_first`` / ``proxy_mae_last``.
+
+``--proxy-cost census`` labels with the census / Hamming pixel cost in place of Birchfield-Tomasi (``StereoSGM(cost=
+"census")``, INTEGRATION.md "The census cost"): it compares the order of the intensities inside each image, not the
+intensities of the two cameras, so the labels do not move under a gain, exposure or gamma difference between the sensors,
+the case the adaptation is for. ``--proxy-census-window HxW`` (rows x columns: 3x3, 5x5, 7x7 or 7x9, default 7x9) is its
+window; both are parameters, not measured optima, and need a positive ``--proxy-weight``. The default stays ``bt``; with
+``census`` the meta also carries ``proxy_cost`` and ``proxy_census_window``.
 """
 
 from __future__ import annotations
@@ -50,7 +58,7 @@ from .selfsup import SelfSupLoss, adapt_epoch, selfsup_params, ssim_param
 
 META_KEYS = ("loss", "photo", "smooth", "visible_fraction")
 PROXY_META_KEYS = ("proxy_loss", "proxy_mae", "proxy_fraction")
-PROXY_DEFAULTS = dict(proxy_num_disparities=64, proxy_block_size=5, proxy_mode="3way")
+PROXY_DEFAULTS = dict(proxy_num_disparities=64, proxy_block_size=5, proxy_mode="3way", proxy_cost="bt")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -88,6 +96,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Disparity range of the labelling matcher (default 64; a multiple of 16).")
     p.add_argument("--proxy-block-size", type=int, default=None, help="Block size of the labelling matcher (default 5).")
     p.add_argument("--proxy-mode", type=str, default=None, help="Path mode of the labelling matcher (default 3way).")
+    p.add_argument("--proxy-cost", type=str, default=None, choices=("bt", "census"),
+                   help="Pixel cost of the labelling matcher (default bt; census is invariant to monotone intensity maps).")
+    p.add_argument("--proxy-census-window", type=str, default=None,
+                   help="Census window HxW, rows x columns: 3x3, 5x5, 7x7 or 7x9 (default 7x9; needs --proxy-cost census).")
     return p
 
 
@@ -103,9 +115,11 @@ def adapt_options(left_dir=None, right_dir=None, dataset_root=None, output_dir=N
                   precision: str = "fp32", w_smooth: float = 0.1, edge_gamma: float = 10.0, occ_tol: float = 0.5,
                   uncertainty: bool = True, max_samples: int = 0, seed: int = 42, base_channels: int = 32,
                   read_threads: int = 16, ssim_weight: float = 0.0, proxy_weight: float = 0.0, proxy_only: bool = False,
-                  proxy_num_disparities=None, proxy_block_size=None, proxy_mode=None) -> dict:
+                  proxy_num_disparities=None, proxy_block_size=None, proxy_mode=None, proxy_cost=None,
+                  proxy_census_window=None) -> dict:
     """The tool's options checked and gathered (raises ValueError), before a model or a device is touched. The proxy
-    options are part of the result only with a positive ``proxy_weight``."""
+    options are part of the result only with a positive ``proxy_weight``, ``proxy_cost`` and ``proxy_census_window``
+    ("HxW") only when the cost is "census" (without them it is "bt")."""
     dirs = left_dir is not None or right_dir is not None
     if (dataset_root is not None) == dirs or (dirs and (left_dir is None or right_dir is None)):
         raise ValueError("give either --dataset-root or both --left-dir and --right-dir")
@@ -137,7 +151,7 @@ def adapt_options(left_dir=None, right_dir=None, dataset_root=None, output_dir=N
     except ValueError as e:
         raise ValueError(f"--ssim-weight: {e}") from None
     proxy = _proxy_options(proxy_weight, proxy_only, proxy_num_disparities, proxy_block_size, proxy_mode, batch_size,
-                           width)
+                           width, proxy_cost, proxy_census_window)
     return dict(left_dir=None if left_dir is None else str(left_dir), right_dir=None if right_dir is None else str(right_dir),
                 dataset_root=None if dataset_root is None else str(dataset_root), output_dir=str(output_dir),
                 height=height, width=width, epochs=int(epochs), batch_size=int(batch_size), lr=float(lr),
@@ -146,7 +160,8 @@ def adapt_options(left_dir=None, right_dir=None, dataset_root=None, output_dir=N
                 base_channels=int(base_channels), read_threads=int(read_threads), ssim_weight=ssim_weight, **proxy)
 
 
-def _proxy_options(weight, only, num_disparities, block_size, mode, batch_size, width) -> dict:
+def _proxy_options(weight, only, num_disparities, block_size, mode, batch_size, width, cost=None,
+                   census_window=None) -> dict:
     """The proxy options checked: {} with the weight at 0 (no other proxy option may then be given)."""
     from .sgm import StereoSGM
 
@@ -154,7 +169,8 @@ def _proxy_options(weight, only, num_disparities, block_size, mode, batch_size, 
         weight = proxy_param(weight)
     except ValueError as e:
         raise ValueError(f"--proxy-weight: {e}") from None
-    given = dict(proxy_num_disparities=num_disparities, proxy_block_size=block_size, proxy_mode=mode)
+    given = dict(proxy_num_disparities=num_disparities, proxy_block_size=block_size, proxy_mode=mode, proxy_cost=cost,
+                 proxy_census_window=census_window)
     if weight == 0:
         if only:
             raise ValueError("--proxy-only needs a positive --proxy-weight")
@@ -162,12 +178,13 @@ def _proxy_options(weight, only, num_disparities, block_size, mode, batch_size, 
         if extra:
             raise ValueError(f"{', '.join(extra)}: the matcher's options need a positive --proxy-weight")
         return {}
-    out = {k: PROXY_DEFAULTS[k] if v is None else v for k, v in given.items()}
+    out = {k: PROXY_DEFAULTS.get(k) if v is None else v for k, v in given.items()}
     try:
         m = StereoSGM(num_disparities=out["proxy_num_disparities"], block_size=out["proxy_block_size"],
-                      mode=out["proxy_mode"])
+                      mode=out["proxy_mode"], cost=out["proxy_cost"], census_window=out["proxy_census_window"])
     except (TypeError, ValueError) as e:
-        raise ValueError(f"--proxy-num-disparities / --proxy-block-size / --proxy-mode: {e}") from None
+        raise ValueError(f"--proxy-num-disparities / --proxy-block-size / --proxy-mode / --proxy-cost / "
+                         f"--proxy-census-window: {e}") from None
     if int(batch_size) > PROXY_MAX_BATCH:
         raise ValueError(f"--batch-size must be <= {PROXY_MAX_BATCH} with --proxy-weight (the matcher's streams), "
                          f"got: {batch_size}")
@@ -176,8 +193,9 @@ def _proxy_options(weight, only, num_disparities, block_size, mode, batch_size, 
             check_width(width, m.min_disparity, m.num_disparities)
         except ValueError as e:
             raise ValueError(f"--width / --proxy-num-disparities: {e}") from None
+    census = {} if m.cost == "bt" else dict(proxy_cost=m.cost, proxy_census_window="%dx%d" % m.census_window)
     return dict(proxy_weight=weight, proxy_only=bool(only), proxy_num_disparities=m.num_disparities,
-                proxy_block_size=m.block_size, proxy_mode=m.mode)
+                proxy_block_size=m.block_size, proxy_mode=m.mode, **census)
 
 
 class _Frames:
@@ -339,7 +357,8 @@ def adapt(checkpoint, *, model=None, device="cuda", **options) -> dict:
         check_width(W, 0, opts["proxy_num_disparities"])
         proxy = ProxyLoss(opts["batch_size"], w_proxy=opts["proxy_weight"], uncertainty=opts["uncertainty"], device=dev,
                           num_disparities=opts["proxy_num_disparities"], block_size=opts["proxy_block_size"],
-                          mode=opts["proxy_mode"])
+                          mode=opts["proxy_mode"], cost=opts.get("proxy_cost", "bt"),
+                          census_window=opts.get("proxy_census_window"))
     loss = None
     if not (use_proxy and opts["proxy_only"]):
         loss = SelfSupLoss(opts["batch_size"], w_smooth=opts["w_smooth"], gamma=opts["edge_gamma"],
@@ -382,7 +401,8 @@ def main(argv=None) -> dict:
                              not a.no_uncertainty, a.max_samples, a.seed, a.base_channels, a.read_threads,
                              a.ssim_weight, proxy_weight=a.proxy_weight, proxy_only=a.proxy_only,
                              proxy_num_disparities=a.proxy_num_disparities, proxy_block_size=a.proxy_block_size,
-                             proxy_mode=a.proxy_mode)
+                             proxy_mode=a.proxy_mode, proxy_cost=a.proxy_cost,
+                             proxy_census_window=a.proxy_census_window)
     except ValueError as e:
         parser.error(str(e))
     _resolve_device(a.device)

@@ -4,7 +4,9 @@
 // is pinned bit for bit to the NumPy restatement tests/sgm_ref.py, not to OpenCV's bytes.
 //   gray / prefilter : byte streaming kernels
 //   cost             : Birchfield-Tomasi pixel cost, bs x bs block sum as a row pass and a column pass -> uint16
-//                      C[y][x][d] (d fastest)
+//                      C[y][x][d] (d fastest). With the census cost ("The census cost") the
+//                      prefilter gives way to a descriptor kernel and the row pass takes the Hamming distance of two
+//                      uint64 descriptors as its pixel cost; the column pass and all that follows are shared
 //   aggregate        : three scan-line recurrences with d across the 64 lanes of a wave (d = lane + 64 k, k < D / 64
 //                      rounded up): top->down writes S, left->right adds to S, right->left keeps its L in registers,
 //                      forms the total and does the winner, the right-view disparity and the left-right check in flight.
@@ -41,7 +43,13 @@ bool sgm_dims_ok(int H, int W) { return H > 0 && W > 0 && (long long)H * W <= IN
 struct SgmParams {
     int minD, D, bs, P1, P2, max_diff, uniq, speckle_window, speckle_range, cap;
     int npaths = 3;  // paths summed into S: 3 (3-way), 4 (hh4), 5 (sgbm), 8 (hh)
+    int nbits = 0;   // census cost: the descriptor's bits (the pixel cost is 0..nbits); 0: Birchfield-Tomasi
 };
+// the census windows (rows x columns) and their descriptor bits wh * ww - 1; 0 for any other window
+int sgm_census_bits(int wh, int ww) {
+    const bool ok = (wh == 3 && ww == 3) || (wh == 5 && ww == 5) || (wh == 7 && ww == 7) || (wh == 7 && ww == 9);
+    return ok ? wh * ww - 1 : 0;
+}
 // the paths of a mode (SD_SGM_MODE_*, cv2's constants), 0 for anything else
 int sgm_mode_paths(int mode) {
     switch (mode) {
@@ -58,7 +66,14 @@ const char* sgm_params_error(const SgmParams& p) {
     if (p.bs % 2 == 0 || p.bs < 3 || p.bs > 11) return "block_size must be odd in [3, 11]";
     if (p.cap < 1 || p.cap > 63) return "pre_filter_cap must be in [1, 63]";
     if (p.P1 < 0 || p.P2 < p.P1) return "0 <= P1 <= P2 required";
-    if ((long long)p.npaths * ((long long)p.bs * p.bs * (2 * p.cap + 63) + p.P2) > 65535)
+    if (p.nbits) {  // census: a pixel cost is at most nbits
+        if (p.nbits != 8 && p.nbits != 24 && p.nbits != 48 && p.nbits != 62) return "nbits must be 8, 24, 48 or 62";
+        if ((long long)p.npaths * ((long long)p.bs * p.bs * p.nbits + p.P2) > 65535)
+            return p.npaths == 3   ? "3 * (bs^2 * nbits + P2) exceeds 65535"
+                   : p.npaths == 4 ? "4 * (bs^2 * nbits + P2) exceeds 65535 (4 paths)"
+                   : p.npaths == 5 ? "5 * (bs^2 * nbits + P2) exceeds 65535 (5 paths)"
+                                   : "8 * (bs^2 * nbits + P2) exceeds 65535 (8 paths)";
+    } else if ((long long)p.npaths * ((long long)p.bs * p.bs * (2 * p.cap + 63) + p.P2) > 65535)
         return p.npaths == 3   ? "3 * (bs^2 * (2 * cap + 63) + P2) exceeds 65535"
                : p.npaths == 4 ? "4 * (bs^2 * (2 * cap + 63) + P2) exceeds 65535 (4 paths)"
                : p.npaths == 5 ? "5 * (bs^2 * (2 * cap + 63) + P2) exceeds 65535 (5 paths)"
@@ -114,6 +129,55 @@ __global__ __launch_bounds__(256) void k_sgm_prefilter(const uint8_t* __restrict
     }
 }
 
+// ------------------------------------------------------------------ stage 2c (census cost)
+// The census descriptor of every pixel of a gray plane ("The census cost", step 2c): bit k is set where
+// the k-th window position, row-major without the centre, holds a value strictly below the centre's; positions outside
+// the image take the nearest pixel of the same image. Block: a tile of 64 columns x 16 rows, staged with its halo in
+// LDS (clamped to the image there, so the descriptor loop has no bounds). A wave walks a row: its 64 lanes read 64
+// adjacent bytes of one LDS row, 16 or 17 dwords in as many banks, the four lanes of a dword one broadcast. Each
+// thread builds the descriptors of four rows (ty, ty + 4, ...) from LDS alone and stores 8 bytes per pixel.
+constexpr int CENSUS_TW = 64, CENSUS_TH = 16;
+template <int WH, int WW>
+__global__ __launch_bounds__(256) void k_sgm_census(const uint8_t* __restrict__ g, int H, int W,
+                                                    unsigned long long* __restrict__ desc, long long img_stride,
+                                                    long long desc_stride) {
+    constexpr int RY = WH / 2, RX = WW / 2, LH = CENSUS_TH + 2 * RY, LW = CENSUS_TW + 2 * RX;
+    __shared__ unsigned char tile[LH][LW];
+    if (const unsigned sid = stream_index(blockIdx.z)) {
+        stream_branch();
+        seek_stream(g, sid, img_stride), seek_stream(desc, sid, desc_stride);
+    }
+    const int x0 = blockIdx.x * CENSUS_TW, y0 = blockIdx.y * CENSUS_TH;
+    for (int i = threadIdx.x; i < LH * LW; i += 256) {
+        const int ly = i / LW, lx = i - ly * LW;
+        const int gy = min(max(y0 + ly - RY, 0), H - 1), gx = min(max(x0 + lx - RX, 0), W - 1);
+        tile[ly][lx] = g[(size_t)gy * W + gx];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, x = x0 + lane;
+    if (x >= W) return;
+#pragma unroll
+    for (int j = 0; j < CENSUS_TH / 4; ++j) {
+        const int ly = (threadIdx.x >> 6) + 4 * j, y = y0 + ly;
+        if (y >= H) break;
+        const unsigned c = tile[ly + RY][lane + RX];
+        unsigned lo = 0, hi = 0;  // bits 0..31 and 32..63: the shifts are compile-time constants
+#pragma unroll
+        for (int dy = 0; dy < WH; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < WW; ++dx) {
+                if (dy == RY && dx == RX) continue;
+                const int k = dy * WW + dx - (dy * WW + dx > RY * WW + RX ? 1 : 0);
+                const unsigned below = tile[ly + dy][lane + dx] < c ? 1u : 0u;
+                if (k < 32)
+                    lo |= below << k;
+                else
+                    hi |= below << (k - 32);
+            }
+        desc[(size_t)y * W + x] = (unsigned long long)hi << 32 | lo;
+    }
+}
+
 // ------------------------------------------------------------------ stages 3, 4
 __device__ __forceinline__ void bt_terms(const uint8_t* __restrict__ row, int x, int W, int& u, int& u0, int& u1) {
     u = row[x];
@@ -135,11 +199,37 @@ __device__ __forceinline__ int bt_plane(const uint8_t* __restrict__ a, const uin
 // Rows: block (segment group, row y), 256 threads = 256 / D segments of SGM_SEG columns x D disparities. A thread
 // slides the bs-wide window of its (segment, d) along x: the pixel costs inside the window live in a ring in LDS
 // (private to the thread: no barrier), their sum in a register. Lanes run along d: 2-byte stores, 128 B per wave.
-__global__ __launch_bounds__(256) void k_sgm_cost_rows(const uint8_t* __restrict__ gl, const uint8_t* __restrict__ gr,
-                                                       const uint8_t* __restrict__ pl, const uint8_t* __restrict__ pr,
-                                                       int W, int minD, int D, int bs, uint16_t* __restrict__ Hs,
-                                                       long long img_stride, long long pre_stride,
-                                                       long long vol_stride) {
+//
+// The pixel cost is the kernel's template parameter: the planes it reads, as kernel arguments, and value(cx, xr), the
+// cost of left column cx against right column xr of the block's row. Both costs are at most 255, the ring's bytes.
+// A cost reads the gray planes, a second kind of plane of its own ("side" planes), or both: seek() moves its pointers to
+// stream sid given the distance between the streams' gray planes and between their side planes, each in elements of
+// the plane. The host takes the second distance from cost_side_stride() below, per cost type, never from the caller.
+struct CostBT {  // step 3: Birchfield-Tomasi of the prefiltered planes + that of the gray planes >> 2
+    const uint8_t *__restrict__ gl, *__restrict__ gr, *__restrict__ pl, *__restrict__ pr;
+    __device__ __forceinline__ void seek(unsigned sid, long long img_stride, long long side_stride) {  // side: pl, pr
+        seek_stream(gl, sid, img_stride), seek_stream(gr, sid, img_stride);
+        seek_stream(pl, sid, side_stride), seek_stream(pr, sid, side_stride);
+    }
+    __device__ __forceinline__ void row(size_t o) { gl += o, gr += o, pl += o, pr += o; }
+    __device__ __forceinline__ int value(int W, int cx, int xr) const {
+        return bt_plane(pl, pr, W, cx, xr) + (bt_plane(gl, gr, W, cx, xr) >> 2);
+    }
+};
+// step 3c: the Hamming distance of the two census descriptors. cx is uniform over the d lanes of a segment (one
+// address, broadcast); xr = cx - d - minD runs contiguously along d: 8 bytes per lane, whole cache lines per wave.
+struct CostCensus {
+    const unsigned long long *__restrict__ cl, *__restrict__ cr;
+    __device__ __forceinline__ void seek(unsigned sid, long long, long long side_stride) {  // side: cl, cr; no gray
+        seek_stream(cl, sid, side_stride), seek_stream(cr, sid, side_stride);
+    }
+    __device__ __forceinline__ void row(size_t o) { cl += o, cr += o; }
+    __device__ __forceinline__ int value(int, int cx, int xr) const { return __popcll(cl[cx] ^ cr[xr]); }
+};
+template <class Cost>
+__global__ __launch_bounds__(256) void k_sgm_cost_rows(Cost cost, int W, int minD, int D, int bs,
+                                                       uint16_t* __restrict__ Hs, long long img_stride,
+                                                       long long side_stride, long long vol_stride) {
     __shared__ unsigned char ring[11][256];
     const int tid = threadIdx.x, spb = 256 / D, seg = tid / D, d = tid - seg * D;
     if (seg >= spb) return;
@@ -149,15 +239,14 @@ __global__ __launch_bounds__(256) void k_sgm_cost_rows(const uint8_t* __restrict
     const int xe = min(xs + SGM_SEG, W);
     if (const unsigned sid = stream_index(blockIdx.z)) {
         stream_branch();
-        seek_stream(gl, sid, img_stride), seek_stream(gr, sid, img_stride);
-        seek_stream(pl, sid, pre_stride), seek_stream(pr, sid, pre_stride), seek_stream(Hs, sid, vol_stride);
+        cost.seek(sid, img_stride, side_stride), seek_stream(Hs, sid, vol_stride);
     }
     const size_t o = (size_t)y * W;
-    gl += o, gr += o, pl += o, pr += o;
+    cost.row(o);
     int sum = 0, last_cx = -1, last_val = 0, slot = 0;
     for (int pos = xs - r; pos <= xs + r; ++pos) {
         const int cx = min(max(pos, maxD), W - 1), xr = cx - d - minD;
-        if (cx != last_cx) last_val = bt_plane(pl, pr, W, cx, xr) + (bt_plane(gl, gr, W, cx, xr) >> 2);
+        if (cx != last_cx) last_val = cost.value(W, cx, xr);
         last_cx = cx;
         ring[slot][tid] = (unsigned char)last_val;
         sum += last_val;
@@ -167,7 +256,7 @@ __global__ __launch_bounds__(256) void k_sgm_cost_rows(const uint8_t* __restrict
     out[(size_t)xs * D] = (uint16_t)sum;
     for (int x = xs + 1; x < xe; ++x) {  // slot: the column that leaves (x - r - 1), replaced by the one that enters
         const int cx = min(x + r, W - 1), xr = cx - d - minD;
-        if (cx != last_cx) last_val = bt_plane(pl, pr, W, cx, xr) + (bt_plane(gl, gr, W, cx, xr) >> 2);
+        if (cx != last_cx) last_val = cost.value(W, cx, xr);
         last_cx = cx;
         sum += last_val - (int)ring[slot][tid];
         ring[slot][tid] = (unsigned char)last_val;
@@ -845,20 +934,44 @@ __global__ __launch_bounds__(256) void k_sgm_center(const float* __restrict__ sr
 struct SgmBatch {
     int n;
     long long img, pre, vol, spk;
+    long long dsc = 0;  // census cost: uint64 elements between the streams' descriptor planes
 };
 constexpr SgmBatch SGM_ONE = {1, 0, 0, 0, 0};
 
-int launch_cost(const SgmBatch& nb, const uint8_t* gl, const uint8_t* gr, const uint8_t* pl, const uint8_t* pr, int H,
-                int W, const SgmParams& p, uint16_t* C, uint16_t* tmp, hipStream_t st) {
+// the distance between the streams' side planes of a cost, in the elements Cost::seek counts in: bytes between the
+// prefiltered planes, uint64 between the descriptor planes
+long long cost_side_stride(const SgmBatch& nb, const CostBT&) { return nb.pre; }
+long long cost_side_stride(const SgmBatch& nb, const CostCensus&) { return nb.dsc; }
+template <class Cost>
+int launch_cost(const SgmBatch& nb, const Cost& cost, int H, int W, const SgmParams& p, uint16_t* C,
+                uint16_t* tmp, hipStream_t st, const char* what) {
     const int maxD = p.minD + p.D;
     if (W <= maxD) return SD_OK;
     const int nseg = cdiv(W - maxD, SGM_SEG), spb = 256 / p.D;
     // grid y is the row (cost_rows) or the row segment (cost_cols): the stream goes in z
-    hipLaunchKernelGGL(k_sgm_cost_rows, dim3(cdiv(nseg, spb), H, nb.n), dim3(256), 0, st, gl, gr, pl, pr, W, p.minD, p.D,
-                       p.bs, tmp, nb.img, nb.pre, nb.vol);
+    hipLaunchKernelGGL(k_sgm_cost_rows<Cost>, dim3(cdiv(nseg, spb), H, nb.n), dim3(256), 0, st, cost, W, p.minD, p.D,
+                       p.bs, tmp, nb.img, cost_side_stride(nb, cost), nb.vol);
     hipLaunchKernelGGL(k_sgm_cost_cols, dim3(cdiv((long long)(W - maxD) * p.D, 1024), cdiv(H, SGM_YSEG), nb.n), dim3(256),
                        0, st, tmp, H, W, maxD, p.D, p.bs, C, nb.vol);
-    return sd_check_launch("sd_sgm_cost");
+    return sd_check_launch(what);
+}
+
+// the descriptors of n planes g [n][H][W] (img_stride apart) into desc (desc_stride apart), one launch
+int launch_census(int n, const uint8_t* g, int H, int W, int wh, int ww, unsigned long long* desc, long long img_stride,
+                  long long desc_stride, hipStream_t st) {
+    const dim3 grid(cdiv(W, CENSUS_TW), cdiv(H, CENSUS_TH), n), b(256);
+#define SGM_CENSUS(WH, WW) \
+    hipLaunchKernelGGL((k_sgm_census<WH, WW>), grid, b, 0, st, g, H, W, desc, img_stride, desc_stride)
+    if (wh == 3)
+        SGM_CENSUS(3, 3);
+    else if (wh == 5)
+        SGM_CENSUS(5, 5);
+    else if (ww == 7)
+        SGM_CENSUS(7, 7);
+    else
+        SGM_CENSUS(7, 9);
+#undef SGM_CENSUS
+    return sd_check_launch("sd_sgm_census");
 }
 
 template <int NK, bool FULL>
@@ -1007,7 +1120,36 @@ extern "C" int sd_sgm_cost(const uint8_t* gray_l, const uint8_t* gray_r, const u
     SD_REQUIRE(sgm_dims_ok(H, W) && H <= 65535, "sd_sgm_cost: bad sizes %dx%d", H, W);
     const SgmParams p = {min_disparity, num_disparities, block_size, 0, 0, 1, 0, 0, 0, 31};
     SGM_PARAMS_OK("sd_sgm_cost", p);
-    return launch_cost(SGM_ONE, gray_l, gray_r, pre_l, pre_r, H, W, p, C, tmp, to_stream(s));
+    return launch_cost(SGM_ONE, CostBT{gray_l, gray_r, pre_l, pre_r}, H, W, p, C, tmp, to_stream(s), "sd_sgm_cost");
+}
+
+extern "C" int sd_sgm_census_n(int n, const uint8_t* gray, int H, int W, int win_h, int win_w, uint64_t* desc,
+                               sd_stream s) {
+    SGM_N_REQUIRE("sd_sgm_census_n", n);
+    SD_REQUIRE(gray && desc, "sd_sgm_census_n: null pointer");
+    SD_REQUIRE((uintptr_t)desc % 8 == 0, "sd_sgm_census_n: desc must be 8-B aligned");
+    SD_REQUIRE(sgm_dims_ok(H, W) && H <= 65535, "sd_sgm_census_n: bad sizes %dx%d", H, W);
+    SD_REQUIRE(sgm_census_bits(win_h, win_w), "sd_sgm_census_n: window %dx%d (3x3, 5x5, 7x7 or 7x9, rows x columns)",
+               win_h, win_w);
+    const long long P = (long long)H * W;
+    return launch_census(n, gray, H, W, win_h, win_w, reinterpret_cast<unsigned long long*>(desc), P, P, to_stream(s));
+}
+
+extern "C" int sd_sgm_cost_census(const uint64_t* desc_l, const uint64_t* desc_r, int H, int W, int min_disparity,
+                                  int num_disparities, int block_size, int nbits, uint16_t* C, uint16_t* tmp,
+                                  sd_stream s) {
+    SD_REQUIRE(desc_l && desc_r && C && tmp && C != tmp, "sd_sgm_cost_census: null pointer");
+    SD_REQUIRE((uintptr_t)desc_l % 8 == 0 && (uintptr_t)desc_r % 8 == 0, "sd_sgm_cost_census: desc must be 8-B aligned");
+    SD_REQUIRE((uintptr_t)C % 8 == 0 && (uintptr_t)tmp % 8 == 0, "sd_sgm_cost_census: volumes must be 8-B aligned");
+    SD_REQUIRE(sgm_dims_ok(H, W) && H <= 65535, "sd_sgm_cost_census: bad sizes %dx%d", H, W);
+    SD_REQUIRE(nbits == 8 || nbits == 24 || nbits == 48 || nbits == 62, "sd_sgm_cost_census: nbits %d (8, 24, 48, 62)",
+               nbits);
+    SgmParams p = {min_disparity, num_disparities, block_size, 0, 0, 1, 0, 0, 0, 31};
+    p.nbits = nbits;
+    SGM_PARAMS_OK("sd_sgm_cost_census", p);
+    const CostCensus cost = {reinterpret_cast<const unsigned long long*>(desc_l),
+                             reinterpret_cast<const unsigned long long*>(desc_r)};
+    return launch_cost(SGM_ONE, cost, H, W, p, C, tmp, to_stream(s), "sd_sgm_cost_census");
 }
 
 extern "C" int sd_sgm_aggregate(const uint16_t* C, int H, int W, int min_disparity, int num_disparities, int P1, int P2,
@@ -1070,18 +1212,27 @@ extern "C" int sd_sgm_speckle_n(int n, int16_t* q, int H, int W, int invalid_val
 namespace {
 // the vertical-family paths a mode adds to the 3-way mode's three, as (dy, dx)
 const int SGM_EXTRA_PATHS[5][2] = {{1, 1}, {1, -1}, {-1, 0}, {-1, 1}, {-1, -1}};
+// One stream's workspace: sd_sgm_ws_bytes, and for the census cost two uint64 descriptor planes behind it, so that the
+// Birchfield-Tomasi layout is a prefix of the census one. A multiple of 256.
+long long sgm_ws_slice(int H, int W, int D, int cost) {
+    return sd_sgm_ws_bytes(H, W, D) + (cost == SD_SGM_COST_CENSUS ? 2 * align256(8ll * H * W) : 0);
+}
 // The whole matcher for n streams: gray_l, gray_r [n][H][W], q [n][H][W], work n slices of sd_sgm_ws_bytes. One launch
-// sequence whatever n is; the single-stream entry points are n = 1.
+// sequence whatever n is; the single-stream entry points are n = 1. p.nbits != 0 is the census cost of window
+// (wh, ww): work is then n slices of sgm_ws_slice(.., SD_SGM_COST_CENSUS), the Birchfield-Tomasi slice followed by the
+// two descriptor planes, and the prefiltered planes stay unwritten.
 int sgm_compute(const char* what, int n, const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, const SgmParams& p,
-                int mode, void* work, int16_t* q, sd_stream s) {
+                int mode, int wh, int ww, void* work, int16_t* q, sd_stream s) {
     SGM_N_REQUIRE(what, n);
     SD_REQUIRE(gray_l && gray_r && work && q, "%s: null pointer (gray_l, gray_r, work, q)", what);
     SD_REQUIRE(sgm_dims_ok(H, W) && H <= 65535 && W <= SGM_MAX_W, "%s: bad sizes %dx%d (W <= %d)", what, H, W, SGM_MAX_W);
     SD_REQUIRE((uintptr_t)work % 256 == 0, "%s: work must be 256-B aligned", what);
     const char* e = sgm_params_error(p);
     SD_REQUIRE(!e, "%s: %s", what, e);
-    const long long P = (long long)H * W, vol = align256(2 * P * p.D), slice = sd_sgm_ws_bytes(H, W, p.D);
-    const SgmBatch nb = {n, P, slice, slice / 2, slice / 4};
+    const bool census = p.nbits != 0;
+    const long long P = (long long)H * W, vol = align256(2 * P * p.D);
+    const long long slice = sgm_ws_slice(H, W, p.D, census ? SD_SGM_COST_CENSUS : SD_SGM_COST_BT);
+    const SgmBatch nb = {n, P, slice, slice / 2, slice / 4, slice / 8};
     char* w = static_cast<char*>(work);
     uint16_t* C = reinterpret_cast<uint16_t*>(w);
     uint16_t* S = reinterpret_cast<uint16_t*>(w + vol);
@@ -1089,10 +1240,20 @@ int sgm_compute(const char* what, int n, const uint8_t* gray_l, const uint8_t* g
     uint8_t* pr = pl + align256(P);
     void* sw = pr + align256(P);
     hipStream_t st = to_stream(s);
-    const dim3 g(sgm_grid(P), n), b(256);
-    hipLaunchKernelGGL(k_sgm_prefilter, g, b, 0, st, gray_l, H, W, p.cap, pl, nb.img, nb.pre);
-    hipLaunchKernelGGL(k_sgm_prefilter, g, b, 0, st, gray_r, H, W, p.cap, pr, nb.img, nb.pre);
-    int rc = launch_cost(nb, gray_l, gray_r, pl, pr, H, W, p, C, S, st);  // S is free until the first path writes it
+    int rc;
+    if (census) {
+        unsigned long long* cl = reinterpret_cast<unsigned long long*>(w + sd_sgm_ws_bytes(H, W, p.D));
+        unsigned long long* cr = cl + align256(8 * P) / 8;
+        rc = launch_census(n, gray_l, H, W, wh, ww, cl, nb.img, nb.dsc, st);
+        if (rc == SD_OK) rc = launch_census(n, gray_r, H, W, wh, ww, cr, nb.img, nb.dsc, st);
+        if (rc == SD_OK) rc = launch_cost(nb, CostCensus{cl, cr}, H, W, p, C, S, st, "sd_sgm_cost_census");
+    } else {
+        const dim3 g(sgm_grid(P), n), b(256);
+        hipLaunchKernelGGL(k_sgm_prefilter, g, b, 0, st, gray_l, H, W, p.cap, pl, nb.img, nb.pre);
+        hipLaunchKernelGGL(k_sgm_prefilter, g, b, 0, st, gray_r, H, W, p.cap, pr, nb.img, nb.pre);
+        // S is free until the first path writes it
+        rc = launch_cost(nb, CostBT{gray_l, gray_r, pl, pr}, H, W, p, C, S, st, "sd_sgm_cost");
+    }
     if (rc == SD_OK) rc = launch_aggregate(nb, 0, C, H, W, p, S, st);
     // successive launches, each S += L: sgbm takes the two downward diagonals, hh4 bottom -> up, hh all five
     const int first = mode == SD_SGM_MODE_HH4 ? 2 : 0;
@@ -1119,7 +1280,31 @@ extern "C" int sd_sgm_compute_n(int n, const uint8_t* gray_l, const uint8_t* gra
     SD_REQUIRE(npaths, "sd_sgm_compute_n: mode %d (SD_SGM_MODE_SGBM 0, _HH 1, _3WAY 2, _HH4 3)", mode);
     const SgmParams p = {min_disparity, num_disparities, block_size, P1, P2, disp12_max_diff, uniqueness_ratio,
                          speckle_window, speckle_range, pre_filter_cap, npaths};
-    return sgm_compute("sd_sgm_compute_n", n, gray_l, gray_r, H, W, p, mode, work, q, s);
+    return sgm_compute("sd_sgm_compute_n", n, gray_l, gray_r, H, W, p, mode, 0, 0, work, q, s);
+}
+
+extern "C" long long sd_sgm_ws_bytes_cost_n(int n, int H, int W, int D, int cost) {
+    const bool ok = sgm_streams_ok(n) && (cost == SD_SGM_COST_BT || cost == SD_SGM_COST_CENSUS);
+    return ok ? n * sgm_ws_slice(H, W, D, cost) : -1;
+}
+
+extern "C" int sd_sgm_compute_cost_n(int n, const uint8_t* gray_l, const uint8_t* gray_r, int H, int W,
+                                     int min_disparity, int num_disparities, int block_size, int P1, int P2,
+                                     int disp12_max_diff, int uniqueness_ratio, int speckle_window, int speckle_range,
+                                     int pre_filter_cap, int mode, int cost, int win_h, int win_w, void* work,
+                                     int16_t* q, sd_stream s) {
+    SGM_N_REQUIRE("sd_sgm_compute_cost_n", n);
+    const int npaths = sgm_mode_paths(mode);
+    SD_REQUIRE(npaths, "sd_sgm_compute_cost_n: mode %d (SD_SGM_MODE_SGBM 0, _HH 1, _3WAY 2, _HH4 3)", mode);
+    SD_REQUIRE(cost == SD_SGM_COST_BT || cost == SD_SGM_COST_CENSUS,
+               "sd_sgm_compute_cost_n: cost %d (SD_SGM_COST_BT 0, SD_SGM_COST_CENSUS 1)", cost);
+    SgmParams p = {min_disparity, num_disparities, block_size, P1, P2, disp12_max_diff, uniqueness_ratio,
+                   speckle_window, speckle_range, pre_filter_cap, npaths};
+    if (cost == SD_SGM_COST_CENSUS) {
+        p.nbits = sgm_census_bits(win_h, win_w);
+        SD_REQUIRE(p.nbits, "sd_sgm_compute_cost_n: window %dx%d (3x3, 5x5, 7x7 or 7x9, rows x columns)", win_h, win_w);
+    }
+    return sgm_compute("sd_sgm_compute_cost_n", n, gray_l, gray_r, H, W, p, mode, win_h, win_w, work, q, s);
 }
 
 extern "C" int sd_sgm_compute(const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
@@ -1128,7 +1313,7 @@ extern "C" int sd_sgm_compute(const uint8_t* gray_l, const uint8_t* gray_r, int 
                               int16_t* q, sd_stream s) {
     const SgmParams p = {min_disparity, num_disparities, block_size, P1, P2, disp12_max_diff, uniqueness_ratio,
                          speckle_window, speckle_range, pre_filter_cap};
-    return sgm_compute("sd_sgm_compute", 1, gray_l, gray_r, H, W, p, SD_SGM_MODE_3WAY, work, q, s);
+    return sgm_compute("sd_sgm_compute", 1, gray_l, gray_r, H, W, p, SD_SGM_MODE_3WAY, 0, 0, work, q, s);
 }
 
 extern "C" int sd_sgm_compute_mode(const uint8_t* gray_l, const uint8_t* gray_r, int H, int W, int min_disparity,
@@ -1139,7 +1324,7 @@ extern "C" int sd_sgm_compute_mode(const uint8_t* gray_l, const uint8_t* gray_r,
     SD_REQUIRE(npaths, "sd_sgm_compute_mode: mode %d (SD_SGM_MODE_SGBM 0, _HH 1, _3WAY 2, _HH4 3)", mode);
     const SgmParams p = {min_disparity, num_disparities, block_size, P1, P2, disp12_max_diff, uniqueness_ratio,
                          speckle_window, speckle_range, pre_filter_cap, npaths};
-    return sgm_compute("sd_sgm_compute_mode", 1, gray_l, gray_r, H, W, p, mode, work, q, s);
+    return sgm_compute("sd_sgm_compute_mode", 1, gray_l, gray_r, H, W, p, mode, 0, 0, work, q, s);
 }
 
 namespace {

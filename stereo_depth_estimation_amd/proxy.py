@@ -105,8 +105,9 @@ class ProxyLoss:
     """A ``StereoSGM``, ``sd_proxy_gray`` and ``sd_proxy_loss`` with their buffers: up to ``streams`` (1..64, the
     matcher's ``MAX_STREAMS``) samples of one size per call. Buffers are made once per size and only grow, and the next
     call overwrites them; ``run`` issues launches only. ``totals`` accumulates the rows of every run on the device;
-    ``means()`` reads them. ``matcher_kw`` are ``StereoSGM``'s other parameters. The defaults are parameters, not
-    measured optima."""
+    ``means()`` reads them. ``matcher_kw`` are ``StereoSGM``'s other parameters, among them ``cost="census"`` and
+    ``census_window=(rows, columns)``: labels from the census / Hamming cost, which a difference in gain, exposure or
+    gamma between the two sensors does not move. The defaults are parameters, not measured optima."""
 
     def __init__(self, streams: int = 16, w_proxy=1.0, uncertainty: bool = True, device="cuda", num_disparities=64,
                  block_size=5, mode="3way", **matcher_kw):
@@ -130,7 +131,8 @@ class ProxyLoss:
                 "num_disparities": m.num_disparities, "block_size": m.block_size, "mode": m.mode, "P1": m.P1, "P2": m.P2,
                 "disp12_max_diff": m.disp12_max_diff, "uniqueness_ratio": m.uniqueness_ratio,
                 "speckle_window_size": m.speckle_window_size, "speckle_range": m.speckle_range,
-                "pre_filter_cap": m.pre_filter_cap}
+                "pre_filter_cap": m.pre_filter_cap, "cost": m.cost,
+                "census_window": None if m.census_window is None else list(m.census_window)}
 
     def _bind_device(self, t: torch.Tensor):
         if self.device.index is None:

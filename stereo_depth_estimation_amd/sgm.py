@@ -18,6 +18,12 @@ The matcher follows OpenCV's StereoSGBM step by step (three paths by default; mo
 bottom-up path, the two downward diagonals or all eight) and is pinned bit for bit to the NumPy restatements
 tests/sgm_ref.py and tests/sgm_modes_ref.py, not to cv2's bytes; what is stated rather than taken from OpenCV is
 listed in INTEGRATION.md. Kernels: csrc/sgm.hip. There is no CPU fallback.
+
+    matcher = StereoSGM(num_disparities=128, block_size=7, cost="census", census_window=(7, 9))
+
+replaces OpenCV's Birchfield-Tomasi pixel cost by the Hamming distance of census descriptors ("The census
+cost"; restated in tests/sgm_census_ref.py): the result does not change under a strictly increasing intensity map of
+either camera. ClassicDepth, ClassicDepthBatch and proxy.ProxyLoss pass ``cost`` and ``census_window`` on to it.
 """
 
 from __future__ import annotations
@@ -49,13 +55,34 @@ def mode_name(mode) -> str:
                      f"got {mode!r}")
 
 
-def ws_bytes(H: int, W: int, D: int) -> int:
+# pixel cost name -> SD_SGM_COST_*; the census windows (rows, columns), their descriptor bits being rows * columns - 1
+COSTS = {"bt": L.SD_SGM_COST_BT, "census": L.SD_SGM_COST_CENSUS}
+CENSUS_WINDOWS = ((3, 3), (5, 5), (7, 7), (7, 9))
+DEFAULT_CENSUS_WINDOW = (7, 9)
+
+
+def parse_census_window(window) -> tuple:
+    """One of CENSUS_WINDOWS as (rows, columns), from a pair or from "HxW" (the tools' spelling, e.g. "7x9")."""
+    w = window
+    try:
+        if isinstance(w, str):
+            w = w.lower().split("x")
+        w = tuple(int(v) for v in w)
+    except (TypeError, ValueError):
+        w = None
+    if w not in CENSUS_WINDOWS:
+        raise ValueError(f"census_window must be one of {', '.join(f'{a}x{b}' for a, b in CENSUS_WINDOWS)} "
+                         f"(rows x columns), got {window!r}")
+    return w
+
+
+def ws_bytes(H: int, W: int, D: int, cost: str = "bt") -> int:
     """sd_sgm_ws_bytes as a formula: two uint16 volumes, two prefiltered planes, the speckle filter's two int32 planes,
-    each rounded up to 256 bytes."""
+    each rounded up to 256 bytes; cost="census" appends the two uint64 descriptor planes (sd_sgm_ws_bytes_cost_n)."""
     def a(v):
         return (v + 255) // 256 * 256
 
-    return 2 * a(2 * H * W * D) + 2 * a(H * W) + 2 * a(4 * H * W)
+    return 2 * a(2 * H * W * D) + 2 * a(H * W) + 2 * a(4 * H * W) + (2 * a(8 * H * W) if cost == "census" else 0)
 
 
 def reprojection_rows(Q) -> np.ndarray:
@@ -72,12 +99,30 @@ def reprojection_rows(Q) -> np.ndarray:
 
 class StereoSGM:
     """cv2.StereoSGBM.create(..., mode=MODE_SGBM_3WAY) of depth_live.py:67-83, parameters by the same names. mode: "3way"
-    (the application's), "hh4", "sgbm" or "hh", or cv2's integer constant."""
+    (the application's), "hh4", "sgbm" or "hh", or cv2's integer constant.
+
+    cost: the pixel cost. "bt" (the default, OpenCV's) is Birchfield-Tomasi on the prefiltered and the gray planes.
+    "census" is the Hamming distance of census descriptors over ``census_window`` = (rows, columns), one of
+    CENSUS_WINDOWS, default (7, 9): it depends only on the order of the intensities inside each image, so any strictly
+    increasing intensity map of either camera (gain, offset, gamma) leaves the result unchanged byte for byte
+    ("The census cost"). P1 and P2 keep their defaults 8 and 32 block_size^2 there: parameters, not
+    measured optima. ``pre_filter_cap`` is then checked and otherwise unused."""
 
     def __init__(self, min_disparity=0, num_disparities=128, block_size=7, P1=None, P2=None, disp12_max_diff=1,
-                 uniqueness_ratio=10, speckle_window_size=100, speckle_range=2, pre_filter_cap=31, mode="3way"):
+                 uniqueness_ratio=10, speckle_window_size=100, speckle_range=2, pre_filter_cap=31, mode="3way",
+                 cost="bt", census_window=None):
         self.mode = mode_name(mode)
         self.mode_id, npaths = MODES[self.mode]
+        if not isinstance(cost, str) or cost not in COSTS:
+            raise ValueError(f"cost must be one of {sorted(COSTS)}, got {cost!r}")
+        if cost == "bt" and census_window is not None:
+            raise ValueError("census_window is the census cost's: give it with cost='census'")
+        self.cost, self.cost_id = cost, COSTS[cost]
+        if cost == "census":
+            self.census_window = parse_census_window(DEFAULT_CENSUS_WINDOW if census_window is None else census_window)
+            self.nbits = self.census_window[0] * self.census_window[1] - 1
+        else:
+            self.census_window, self.nbits = None, None
         minD, D, bs = int(min_disparity), int(num_disparities), int(block_size)
         if D % 16 != 0:
             raise ValueError("--num-disparities must be a multiple of 16.")
@@ -96,7 +141,13 @@ class StereoSGM:
             raise ValueError("pre_filter_cap must be in [1, 63]")
         if P1 < 0 or P2 < P1:
             raise ValueError("0 <= P1 <= P2 required")
-        if npaths * (bs * bs * (2 * cap + 63) + P2) > 65535:
+        if cost == "census":
+            if npaths * (bs * bs * self.nbits + P2) > 65535:
+                raise ValueError(f"{npaths} * (block_size^2 * nbits + P2) = {npaths * (bs * bs * self.nbits + P2)} "
+                                 f"exceeds 65535 (nbits = {self.nbits}, the {self.census_window[0]}x"
+                                 f"{self.census_window[1]} census window): the cost sums of the {npaths} paths of mode "
+                                 f"{self.mode!r} would not fit uint16")
+        elif npaths * (bs * bs * (2 * cap + 63) + P2) > 65535:
             raise ValueError(f"{npaths} * (block_size^2 * (2 * pre_filter_cap + 63) + P2) = "
                              f"{npaths * (bs * bs * (2 * cap + 63) + P2)} exceeds 65535: the cost sums of the "
                              f"{npaths} paths of mode {self.mode!r} would not fit uint16")
@@ -122,13 +173,14 @@ class StereoSGM:
                 self.uniqueness_ratio, self.speckle_window_size, self.speckle_range, self.pre_filter_cap)
 
     def workspace(self, device, H: int, W: int, n: int = 1) -> torch.Tensor:
-        """The matcher's scratch memory for n pairs of H x W (sd_sgm_ws_bytes_n: n x 160 MB at 640 x 480, D = 128).
+        """The matcher's scratch memory for n pairs of H x W (sd_sgm_ws_bytes_cost_n: n x 160 MB at 640 x 480, D = 128,
+        and n x 5 MB of descriptors more with the census cost).
         Nothing is kept in it between calls, so the one buffer serves every size it is large enough for: it is
         replaced only to grow or to change device."""
         key = (device, H, W, n)
         if self._ws_key == key:  # the size of the last call: nothing to ask or to compare
             return self._ws
-        size = L.call("sd_sgm_ws_bytes_n", n, H, W, self.num_disparities)
+        size = L.call("sd_sgm_ws_bytes_cost_n", n, H, W, self.num_disparities, self.cost_id)
         if size < 0:
             raise ValueError(f"streams must be in [1, {MAX_STREAMS}], got {n}")
         if self._ws is None or self._ws_key[0] != device or self._ws.numel() < size:
@@ -174,8 +226,14 @@ class StereoSGM:
             raise ValueError("out must be a contiguous int16 [n, H, W] tensor on the images' device")
         ws = self.workspace(gray_l.device, H, W, n)
         with torch.cuda.device(gray_l.device):
-            L.call("sd_sgm_compute_n", n, gray_l.data_ptr(), gray_r.data_ptr(), H, W, *self.params(), self.mode_id,
-                   ws.data_ptr(), out.data_ptr(), L.stream_handle(gray_l.device))
+            if self.cost == "bt":  # the entry point the step has always called (sd_sgm_compute_cost_n with
+                # SD_SGM_COST_BT is the same host function and the same launches)
+                L.call("sd_sgm_compute_n", n, gray_l.data_ptr(), gray_r.data_ptr(), H, W, *self.params(), self.mode_id,
+                       ws.data_ptr(), out.data_ptr(), L.stream_handle(gray_l.device))
+            else:
+                L.call("sd_sgm_compute_cost_n", n, gray_l.data_ptr(), gray_r.data_ptr(), H, W, *self.params(),
+                       self.mode_id, self.cost_id, *self.census_window, ws.data_ptr(), out.data_ptr(),
+                       L.stream_handle(gray_l.device))
         return out
 
 
@@ -218,7 +276,8 @@ class ClassicDepthBatch:
         attributes (map_l_1, map_l_2, map_r_1, map_r_2, image_size), e.g. load_calibration(path).rectification, shared
         by all streams, or a list of one per stream (all of one image_size). Q: the 4 x 4 reprojection matrix of the
         calibration file for all streams, or [n, 4, 4]. colormap: a name of live.COLORMAP_NAMES or a [256, 3] uint8
-        BGR table. matcher_kw: StereoSGM's parameters."""
+        BGR table. matcher_kw: StereoSGM's parameters, ``cost="census"`` and ``census_window=(rows, columns)`` among
+        them (the census / Hamming pixel cost in place of Birchfield-Tomasi)."""
         n = int(n)
         if not 1 <= n <= MAX_STREAMS:
             raise ValueError(f"streams must be in [1, {MAX_STREAMS}], got {n}")

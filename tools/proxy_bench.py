@@ -17,6 +17,12 @@ Third: ms per ``adapt_step`` with ``proxy=`` (photometric + proxy), labels only,
 code path) of the full-width model at 64 x 240x320 in bf16, in alternating rounds.
 
     python tools/proxy_bench.py --json profiles/proxy_bench.json
+
+``--census-window HxW`` adds, in the same alternating rounds, the matcher and the two proxy steps with the census /
+Hamming pixel cost of that window (``ProxyLoss(cost="census")``): ``matcher_census``, ``adapt_step_proxy_census`` and
+``adapt_step_proxy_only_census``, and their ratios to the Birchfield-Tomasi figures.
+
+    python tools/proxy_bench.py --census-window 7x9 --json profiles/proxy_census_bench.json
 """
 
 from __future__ import annotations
@@ -87,6 +93,7 @@ def rounds_of(fns: dict, iters: dict, rounds: int) -> dict:
 def bench_stages(a, dev) -> dict:
     x, disp, logvar = scene(dev)
     px = proxy.ProxyLoss(B, device=dev, **MATCHER)
+    pc = proxy.ProxyLoss(B, device=dev, cost="census", census_window=a.census_window, **MATCHER) if a.census_window else None
     q4 = px.labels(x).clone()
     stream = lambda: L.stream_handle(dev)  # noqa: E731 (the current stream: a graph capture has its own)
     n = B * H * W
@@ -104,10 +111,11 @@ def bench_stages(a, dev) -> dict:
     fns = {"gray": lambda: L.call("sd_proxy_gray", B, x.data_ptr(), H, W, gray[0].data_ptr(), gray[1].data_ptr(),
                                   stream()),
            "matcher": lambda: px.matcher.compute_batch(gray[0], gray[1], out=q_out),
+           **({"matcher_census": lambda: pc.matcher.compute_batch(gray[0], gray[1], out=q_out)} if pc else {}),
            "loss_accumulate": loss_call(1), "loss_overwrite": loss_call(0),
            "torch_loss": lambda: torch_loss(disp, logvar, q4, 1.0)}
-    iters = {"gray": a.iters, "matcher": a.matcher_iters, "loss_accumulate": a.iters, "loss_overwrite": a.iters,
-             "torch_loss": a.torch_iters}
+    iters = {"gray": a.iters, "matcher": a.matcher_iters, "matcher_census": a.matcher_iters, "loss_accumulate": a.iters,
+             "loss_overwrite": a.iters, "torch_loss": a.torch_iters}
     # the two forms' numbers on the same tensors
     fns["loss_overwrite"]()
     ref = torch_loss(disp, logvar, q4, 1.0)
@@ -116,7 +124,7 @@ def bench_stages(a, dev) -> dict:
              "glogvar_max_diff_vs_torch_rel": float((gl - ref[1]).abs().max() / ref[1].abs().max()),
              "torch_loss_value": float(ref[2]), **summary}
     for k, fn in fns.items():
-        _events(fn, 3 if k in ("matcher", "torch_loss") else a.warmup, 3)
+        _events(fn, 3 if k in ("matcher", "matcher_census", "torch_loss") else a.warmup, 3)
     out = rounds_of(fns, iters, a.rounds)
     for k in ("loss_accumulate", "loss_overwrite"):
         out[k]["ms_per_call_graph_replay"] = _graph_ms(fns[k], a.iters)
@@ -126,6 +134,10 @@ def bench_stages(a, dev) -> dict:
     acc["achieved_GBps_graph_replay"] = acc["bytes_moved"] / (acc["ms_per_call_graph_replay"] * 1e-3) / 1e9
     out["loss_speedup_vs_torch"] = out["torch_loss"]["ms_per_call"] / out["loss_overwrite"]["ms_per_call"]
     out.update(batch=B, H=H, W=W, pixels=n, matcher_params=MATCHER, **diffs)
+    if pc:
+        out["census_window"] = "%dx%d" % pc.matcher.census_window
+        out["matcher_census_over_matcher"] = out["matcher_census"]["ms_per_call"] / out["matcher"]["ms_per_call"]
+        out["census_labels"] = pc.run(disp, logvar, x).summary()
     print(json.dumps(out))
     return out
 
@@ -144,6 +156,10 @@ def bench_step(a, dev) -> dict:
     fns = {"adapt_step": lambda: selfsup.adapt_step(m, opt, x, loss),
            "adapt_step_proxy": lambda: selfsup.adapt_step(m, opt, x, loss, proxy=px),
            "adapt_step_proxy_only": lambda: selfsup.adapt_step(m, opt, x, None, proxy=px)}
+    if a.census_window:
+        pc = proxy.ProxyLoss(B, device=dev, cost="census", census_window=a.census_window, **MATCHER)
+        fns["adapt_step_proxy_census"] = lambda: selfsup.adapt_step(m, opt, x, loss, proxy=pc)
+        fns["adapt_step_proxy_only_census"] = lambda: selfsup.adapt_step(m, opt, x, None, proxy=pc)
     for fn in fns.values():
         _events(fn, a.step_warmup, a.step_warmup)
     out = rounds_of(fns, {k: a.step_iters for k in fns}, a.rounds)
@@ -153,6 +169,12 @@ def bench_step(a, dev) -> dict:
                proxy_over_adapt=out["adapt_step_proxy"]["ms_per_call"] / base,
                proxy_only_over_adapt=out["adapt_step_proxy_only"]["ms_per_call"] / base,
                means=loss.means(), proxy_means=px.means())
+    if a.census_window:
+        out.update(census_window="%dx%d" % pc.matcher.census_window,
+                   proxy_census_over_proxy=out["adapt_step_proxy_census"]["ms_per_call"]
+                   / out["adapt_step_proxy"]["ms_per_call"],
+                   proxy_only_census_over_proxy_only=out["adapt_step_proxy_only_census"]["ms_per_call"]
+                   / out["adapt_step_proxy_only"]["ms_per_call"], proxy_census_means=pc.means())
     print(json.dumps(out))
     return out
 
@@ -166,6 +188,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--step-warmup", type=int, default=4)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--census-window", type=str, default=None,
+                    help="HxW: also time the matcher and the proxy steps with the census cost of this window.")
     ap.add_argument("--json", type=str, default=None, help="Write the results here.")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():

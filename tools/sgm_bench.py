@@ -18,6 +18,11 @@ tool splits it).
 
     python tools/sgm_bench.py --frames 640x480 --num-disparities 128 --block-size 7 --mode hh --json out.json
     python tools/sgm_bench.py --streams 8 --mode 3way
+    python tools/sgm_bench.py --cost census --census-window 7x9
+
+--cost census runs the frame with the census / Hamming pixel cost (StereoSGM(cost="census")): the stage table then
+holds the two descriptor launches ("census (x2)") and the census cost stage in place of the two prefilter launches and
+the Birchfield-Tomasi cost stage they replace.
 """
 
 from __future__ import annotations
@@ -94,12 +99,20 @@ EXTRA_PATHS = {"3way": (), "hh4": ((-1, 0),), "sgbm": ((1, 1), (1, -1)),
                "hh": ((1, 1), (1, -1), (-1, 0), (-1, 1), (-1, -1))}
 
 
-def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str = "3way") -> dict:
+def _cost_kw(cost: str, window) -> dict:
+    """StereoSGM's two keywords; a window with cost "bt" is passed on, so that the constructor refuses it."""
+    return {"cost": cost, **({} if window is None else {"census_window": window})}
+
+
+def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str = "3way", cost: str = "bt",
+          window=None) -> dict:
     dev = torch.device("cuda", torch.cuda.current_device())
     (fl, fr), rect, Q = _scene(np.random.default_rng(0), wc, hc)
-    cd = sgm.ClassicDepth(rectification=rect, Q=Q, num_disparities=D, block_size=bs, mode=mode, device=dev)
-    out = {"frames": f"{wc}x{hc}", "num_disparities": D, "block_size": bs, "mode": mode, "iters": iters, "warmup": warmup,
-           "clock_mhz_before": clock_probe(dev)}
+    cd = sgm.ClassicDepth(rectification=rect, Q=Q, num_disparities=D, block_size=bs, mode=mode, device=dev,
+                          **_cost_kw(cost, window))
+    out = {"frames": f"{wc}x{hc}", "num_disparities": D, "block_size": bs, "mode": mode, "cost": cost,
+           "census_window": None if cost == "bt" else "%dx%d" % cd.matcher.census_window, "iters": iters,
+           "warmup": warmup, "clock_mhz_before": clock_probe(dev)}
 
     def frame():
         cd.step(fl, fr).readout()
@@ -120,20 +133,34 @@ def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str 
     pl = ws.data_ptr() + 2 * vol
     pr = pl + (P + 255) // 256 * 256
     sw = pr + (P + 255) // 256 * 256
+    dl = ws.data_ptr() + L.call("sd_sgm_ws_bytes", H, W, D)  # census: the descriptor planes follow the BT layout
+    dr = dl + (8 * P + 255) // 256 * 256
     fld, frd = b["frames"][0][0], b["frames"][0][1]
     gl, gr = b["gray"][0], b["gray"][1]
     q_tmp = torch.empty_like(q)
     Q = np.ascontiguousarray(cd.Q)
     agg = (C, H, W, m.min_disparity, D, m.P1, m.P2)
+    if cost == "census":
+        wh, ww = m.census_window
+        cost_stages = {
+            "census (x2)": lambda: [L.call("sd_sgm_census_n", 1, g.data_ptr(), H, W, wh, ww, d, s)
+                                    for g, d in ((gl, dl), (gr, dr))],
+            "census cost": lambda: L.call("sd_sgm_cost_census", dl, dr, H, W, m.min_disparity, D, bs, m.nbits, C, S, s),
+        }
+    else:
+        cost_stages = {
+            "prefilter (x2)": lambda: [L.call("sd_sgm_prefilter", g.data_ptr(), H, W, m.pre_filter_cap, p, s)
+                                       for g, p in ((gl, pl), (gr, pr))],
+            "cost": lambda: L.call("sd_sgm_cost", gl.data_ptr(), gr.data_ptr(), pl, pr, H, W, m.min_disparity, D, bs, C, S,
+                                   s),
+        }
     stages = {
         "rectify (x2)": lambda: [L.call("sd_live_rectify", f.data_ptr(), H, W, b[f"m1{k}"].data_ptr(),
                                         b[f"m2{k}"].data_ptr(), b["rect"][i].data_ptr(), s)
                                  for i, (f, k) in enumerate(((fld, "l"), (frd, "r")))],
         "gray (x2)": lambda: [L.call("sd_sgm_gray", b["rect"][i].data_ptr(), H, W, b["gray"][i].data_ptr(), s)
                               for i in range(2)],
-        "prefilter (x2)": lambda: [L.call("sd_sgm_prefilter", g.data_ptr(), H, W, m.pre_filter_cap, p, s)
-                                   for g, p in ((gl, pl), (gr, pr))],
-        "cost": lambda: L.call("sd_sgm_cost", gl.data_ptr(), gr.data_ptr(), pl, pr, H, W, m.min_disparity, D, bs, C, S, s),
+        **cost_stages,
         "aggregate top-down": lambda: L.call("sd_sgm_aggregate", *agg, 0, S, s),
         "aggregate right-left + winner": lambda: L.call("sd_sgm_winner", C, S, H, W, m.min_disparity, D, m.P1, m.P2,
                                                         m.uniqueness_ratio, m.disp12_max_diff, None, None,
@@ -154,7 +181,8 @@ def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str 
     out["stage_us"] = {k: 1e3 * _events(fn, iters, warmup)[0] for k, fn in stages.items()}
     out["stages_ms_sum"] = sum(out["stage_us"].values()) / 1e3
     volume_bytes = 2 * P * D
-    passes = {"cost": 1, "aggregate top-down": 2, "aggregate left-right": 3, "aggregate right-left + winner": 2}
+    out["cost_stages_us"] = sum(out["stage_us"][k] for k in cost_stages)  # what the choice of pixel cost decides
+    passes = {"census cost" if cost == "census" else "cost": 1, "aggregate top-down": 2, "aggregate left-right": 3, "aggregate right-left + winner": 2}
     extra = [k for k in stages if k.endswith("adding")]
     passes.update({k: 3 for k in extra})
     out["volume_bytes"] = volume_bytes
@@ -174,7 +202,7 @@ def bench(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str 
 
 
 def bench_streams(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mode: str, n: int,
-                  batch_only: bool = False) -> dict:
+                  batch_only: bool = False, cost: str = "bt", window=None) -> dict:
     """ClassicDepthBatch(n) against n ClassicDepth objects in turn: every stream has frames of its own, the maps and Q
     are shared. A frame of the batch is step + readout (one sync); the n single objects are timed both with a readout
     after every step (n syncs, what n independent loops do) and with all steps issued before the n readouts.
@@ -184,9 +212,11 @@ def bench_streams(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mo
     fl = np.stack([sc[0][0] for sc in scenes])
     fr = np.stack([sc[0][1] for sc in scenes])
     rect, Q = scenes[0][1], scenes[0][2]
-    kw = dict(rectification=rect, Q=Q, num_disparities=D, block_size=bs, mode=mode, device=dev)
-    out = {"frames": f"{wc}x{hc}", "num_disparities": D, "block_size": bs, "mode": mode, "iters": iters, "warmup": warmup,
-           "streams": n, "workspace_bytes": L.call("sd_sgm_ws_bytes_n", n, hc, wc, D), "clock_mhz_before": clock_probe(dev)}
+    kw = dict(rectification=rect, Q=Q, num_disparities=D, block_size=bs, mode=mode, device=dev, **_cost_kw(cost, window))
+    out = {"frames": f"{wc}x{hc}", "num_disparities": D, "block_size": bs, "mode": mode, "cost": cost,
+           "census_window": None, "iters": iters, "warmup": warmup, "streams": n,
+           "workspace_bytes": L.call("sd_sgm_ws_bytes_cost_n", n, hc, wc, D, sgm.COSTS[cost]),
+           "clock_mhz_before": clock_probe(dev)}
     batch = sgm.ClassicDepthBatch(n, **kw)
     singles = [] if batch_only else [sgm.ClassicDepth(**kw) for _ in range(n)]
 
@@ -212,6 +242,7 @@ def bench_streams(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mo
     torch.cuda.synchronize()
     q = res.disparity_q4
     m = batch.matcher
+    out["census_window"] = None if m.census_window is None else "%dx%d" % m.census_window
     out["valid_fraction"] = float((q[:, :, D:] != m.invalid_value).float().mean())
     if not batch_only:
         one = singles[0].step(fl[0], fr[0])
@@ -231,8 +262,9 @@ def bench_streams(wc: int, hc: int, D: int, bs: int, iters: int, warmup: int, mo
                                  for i, k in enumerate("lr")],
         "gray (x2)": lambda: [L.call("sd_sgm_gray", b["rect"][i].data_ptr(), n * H, W, b["gray"][i].data_ptr(), s)
                               for i in range(2)],
-        "matcher": lambda: L.call("sd_sgm_compute_n", n, b["gray"][0].data_ptr(), b["gray"][1].data_ptr(), H, W,
-                                  *m.params(), m.mode_id, ws.data_ptr(), q_tmp.data_ptr(), s),
+        "matcher": lambda: L.call("sd_sgm_compute_cost_n", n, b["gray"][0].data_ptr(), b["gray"][1].data_ptr(), H, W,
+                                  *m.params(), m.mode_id, m.cost_id, *(m.census_window or (0, 0)), ws.data_ptr(),
+                                  q_tmp.data_ptr(), s),
         "speckle alone": lambda: (q_tmp.copy_(q), L.call("sd_sgm_speckle_n", n, q_tmp.data_ptr(), H, W, m.invalid_value,
                                                          m.speckle_window_size, m.speckle_range, sw.data_ptr(), s)),
         "post": lambda: L.call("sd_sgm_post_n", n, q.data_ptr(), H, W, b["Q"].data_ptr(), b["disp"].data_ptr(),
@@ -253,6 +285,8 @@ def main() -> None:
     ap.add_argument("--num-disparities", type=int, default=128)
     ap.add_argument("--block-size", type=int, default=7)
     ap.add_argument("--mode", choices=sorted(sgm.MODES), default="3way")
+    ap.add_argument("--cost", choices=sorted(sgm.COSTS), default="bt", help="pixel cost of the matcher")
+    ap.add_argument("--census-window", default=None, help="HxW, rows x columns (default 7x9; with --cost census)")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--streams", type=int, default=0,
@@ -265,10 +299,10 @@ def main() -> None:
     w, h = (int(v) for v in args.frames.lower().split("x"))
     if args.streams:
         r = bench_streams(w, h, args.num_disparities, args.block_size, args.iters, args.warmup, args.mode, args.streams,
-                          args.batch_only)
+                          args.batch_only, args.cost, args.census_window)
         print(json.dumps(r), flush=True)
         print(f"\n{r['streams']} streams of {r['frames']}, D = {r['num_disparities']}, bs = {r['block_size']}, mode "
-              f"{r['mode']}; workspace {r['workspace_bytes'] / 1e6:.0f} MB; clock {r['clock_mhz_before']} / "
+              f"{r['mode']}, cost {r['cost']}{'' if r['census_window'] is None else ' ' + r['census_window']}; workspace {r['workspace_bytes'] / 1e6:.0f} MB; clock {r['clock_mhz_before']} / "
               f"{r['clock_mhz_after']} MHz; valid {r['valid_fraction']:.2f}; stream 0 equals the single-stream step: "
               f"{r.get('stream0_equals_single', 'not compared')}")
         print("\n| path | ms per step (events) | ms per step (wall) | frames/s |\n|---|---|---|---|")
@@ -282,10 +316,11 @@ def main() -> None:
             args.json.parent.mkdir(parents=True, exist_ok=True)
             args.json.write_text(json.dumps(r, indent=1))
         return
-    r = bench(w, h, args.num_disparities, args.block_size, args.iters, args.warmup, args.mode)
+    r = bench(w, h, args.num_disparities, args.block_size, args.iters, args.warmup, args.mode, args.cost,
+              args.census_window)
     print(json.dumps(r), flush=True)
-    print(f"\nframe {r['frames']}, D = {r['num_disparities']}, bs = {r['block_size']}, mode {r['mode']}: "
-          f"{r['frame_ms_events']:.3f} ms (events) / {r['frame_ms_wall']:.3f} ms (wall) per step + readout; "
+    print(f"\nframe {r['frames']}, D = {r['num_disparities']}, bs = {r['block_size']}, mode {r['mode']}, cost "
+          f"{r['cost']}{'' if r['census_window'] is None else ' ' + r['census_window']}: {r['frame_ms_events']:.3f} ms (events) / {r['frame_ms_wall']:.3f} ms (wall) per step + readout; "
           f"clock {r['clock_mhz_before']} / {r['clock_mhz_after']} MHz; valid {r['valid_fraction']:.2f}")
     print("\n| stage | us | volume GB/s | ns per chain step |\n|---|---|---|---|")
     for k, us in r["stage_us"].items():
