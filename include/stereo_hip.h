@@ -704,6 +704,40 @@ long long sd_disp_export_ws_bytes(int batch, int Hs, int Ws);
 int sd_disp_export(const float* disp, const float* logvar, int batch, int H, int W, const uint8_t* gt_rgb, int Hs,
                    int Ws, uint8_t* disp_rgb, uint8_t* sigma_rgb, float* disp_up, double* metrics, void* work,
                    sd_stream s);
+/* Uncertainty evaluation (stereo_depth_estimation_amd/uncert.py; no counterpart in the reference): how well the
+ * log-variance head ranks and sizes the errors of the disparity head, against the native ground truth, without a sort.
+ * The contract is sd_disp_export's: allocates nothing, does not synchronise, graph-capturable (a memset node and two
+ * launches), every argument checked before any launch. All arithmetic float32, nothing fused, unless it says otherwise.
+ * Per output pixel of sample b at the frame's own size [Hs][Ws]:
+ *   d, lv, gt  exactly sd_disp_export's: d = the resize of disp with mul = float32(Ws / float(W)), lv = the resize of
+ *              logvar with mul = 1, gt = the decoded RGB24 ground truth
+ *   counted    gt > 0 and d finite and lv finite
+ *   e  = |d - gt|;  q = min(rint(e * 4096), 2^30) as an integer (the product is exact, ties to even). Every error sum of
+ *              the curves is a sum of q: integers, so no summation order exists.
+ *   u  = the uncertainty bin: t = (lv + 32.f) * 64.f; 0 if t < 0, 4095 if t >= 4095, else (int)floorf(t): 1/64 steps of
+ *              log-variance over [-32, 32), the ends saturate
+ *   o  = the oracle bin: clip((bits(e) >> 15) - (119 << 8), 0, 4095): 256 bins per octave over e in [2^-8, 2^8) px
+ *   e_m = e / mul (model pixels);  nll_px = e_m * expf(-lv) + lv (train.py:339 of the reference)
+ *   covered at z in {0.5, 1, 2, 3}: e_m <= z * expf(lv) (Laplace with b = exp(logvar): nominal share 1 - exp(-z))
+ * Per sample, from the histograms cnt_u, sum_u and cnt_o, sum_o [4096] (uint32 counts, uint64 sums of q), n = sum cnt:
+ *   for k = 0 .. steps - 1: keep m_k = n - floor(n k / steps) pixels (64-bit integers); j = the bin with
+ *   C_{<j} < m_k <= C_{<=j}, cumulating upwards from bin 0;
+ *   curve_k = ((double)S_{<j} + (double)(m_k - C_{<j}) * (double)sum_j / (double)cnt_j) / (double)m_k / 4096.0, the
+ *   operations in that order in fp64 (S_{<j} = the integer sum of sum_i over i < j): the pixels of the bin the cut falls
+ *   into share the cut, each entering with the bin's mean error. unc_k from the u histogram, orc_k from the o histogram.
+ *   AUSE = (sum_k ((unc_k - orc_k) / unc_0)) / steps, AURG = (sum_k (1 - unc_k / unc_0)) / steps, each term formed and
+ *   added in index order in fp64; both 0 when unc_0 == 0.
+ * rows f64 [B][16 + 2 steps]: [0] n, [1] sum q as a double (the integer rounded once), [2] sum nll_px accumulated in fp64
+ * (one fixed order: a thread's pixels in index order, block_partial_row, the partial rows in index order), [3..6] the
+ * coverage counts at z = 0.5, 1, 2, 3, [7] AUSE, [8] AURG, [9] counted pixels in u bin 0 or 4095, [10] the same for o,
+ * [11..15] 0, then unc[steps], then orc[steps]. A sample without a counted pixel gets a row of zeros. Integer atomics
+ * only: a sample's row depends neither on launch order nor on the rest of the batch, and two runs give the same 64 bits.
+ * steps in 1..256; rows and work 8-B aligned; work: sd_uncert_eval_ws_bytes(batch, Hs, Ws, steps) bytes, needs no clearing
+ * by the caller (the entry point clears the histograms itself with a memset node ahead of the first launch); -1 for
+ * steps outside 1..256 or sizes outside sd_disp_export's (batch 1..65535, Hs * Ws < 2^31 - 3). */
+long long sd_uncert_eval_ws_bytes(int batch, int Hs, int Ws, int steps);
+int sd_uncert_eval(const float* disp, const float* logvar, int batch, int H, int W, const uint8_t* gt_rgb, int Hs,
+                   int Ws, int steps, double* rows, void* work, sd_stream s);
 /* Host only: n images rgb u8 [n][H][W][3] -> PNG files (8-bit RGB, not interlaced, filter type 0 on every row, one zlib
  * stream at `level` 0..9 in one IDAT chunk), by at most min(threads, 16) threads. File handling as
  * sd_write_cache_batch: each file is written under <name>.tmp.<pid>.<serial> beside its target and renamed over it; a

@@ -235,6 +235,9 @@ PROTOTYPES: dict[str, tuple] = {
     "sd_disp_export_ws_bytes": (ctypes.c_longlong, [_i, _i, _i]),
     "sd_disp_export": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "sd_write_png_batch": (_i, [_p, _i, _i, _i, _p, _i, _i, ctypes.c_char_p, _i]),
+    # uncertainty evaluation: sparsification curves, AUSE / AURG, coverage and the NLL sum from integer histograms
+    "sd_uncert_eval_ws_bytes": (ctypes.c_longlong, [_i, _i, _i, _i]),
+    "sd_uncert_eval": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     # coloured point clouds: reprojection + ordered compaction, and the PLY writer
     "sd_cloud_ws_bytes": (ctypes.c_longlong, [_i, _i, _i, _i]),
     "sd_cloud_build_n": (_i, [_i, _p, _p, _i, _i, _i, _p, _f, _f, _i, _p, _p, ctypes.c_longlong, _p, _p, _p]),

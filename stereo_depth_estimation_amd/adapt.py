@@ -6,7 +6,7 @@
         [--w-smooth 0.1] [--edge-gamma 10] [--occ-tol 0.5] [--no-uncertainty] [--max-samples 0] [--seed 42] \\
         [--base-channels 32] [--read-threads 16] [--device cuda] [--ssim-weight 0] \\
         [--proxy-weight 0] [--proxy-only] [--proxy-num-disparities 64] [--proxy-block-size 5] [--proxy-mode 3way] \\
-        [--proxy-cost bt|census] [--proxy-census-window 7x9]
+        [--proxy-cost bt|census] [--proxy-census-window 7x9] [--eval-uncertainty]
 
 Runs ``selfsup.adapt_epoch`` over the pairs: the photometric + smoothness objective of ``sd_selfsup_loss`` (selfsup.py,
 INTEGRATION.md "sd_selfsup_loss") through the model's training forward, the hand-scheduled backward and AdamW. The frames
@@ -39,6 +39,11 @@ intensities of the two cameras, so the labels do not move under a gain, exposure
 the case the adaptation is for. ``--proxy-census-window HxW`` (rows x columns: 3x3, 5x5, 7x7 or 7x9, default 7x9) is its
 window; both are parameters, not measured optima, and need a positive ``--proxy-weight``. The default stays ``bt``; with
 ``census`` the meta also carries ``proxy_cost`` and ``proxy_census_window``.
+
+``--eval-uncertainty`` (needs ``--dataset-root``) also measures the log-variance head before and after, since the
+adaptation losses push on it: ``sd_uncert_eval`` on the same maps (uncert.py, INTEGRATION.md "Uncertainty evaluation"),
+20 cuts. The meta gains ``eval_uncertainty`` and ``uncertainty_before`` / ``uncertainty_after`` (``uncert.aggregate_rows``:
+NLL, coverage, AUSE, AURG, the sparsification curves); without the flag it is what it was.
 """
 
 from __future__ import annotations
@@ -100,6 +105,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Pixel cost of the labelling matcher (default bt; census is invariant to monotone intensity maps).")
     p.add_argument("--proxy-census-window", type=str, default=None,
                    help="Census window HxW, rows x columns: 3x3, 5x5, 7x7 or 7x9 (default 7x9; needs --proxy-cost census).")
+    p.add_argument("--eval-uncertainty", action="store_true",
+                   help="Also evaluate the log-variance head before and after: sparsification, AUSE, coverage, NLL "
+                        "(needs --dataset-root).")
     return p
 
 
@@ -116,15 +124,17 @@ def adapt_options(left_dir=None, right_dir=None, dataset_root=None, output_dir=N
                   uncertainty: bool = True, max_samples: int = 0, seed: int = 42, base_channels: int = 32,
                   read_threads: int = 16, ssim_weight: float = 0.0, proxy_weight: float = 0.0, proxy_only: bool = False,
                   proxy_num_disparities=None, proxy_block_size=None, proxy_mode=None, proxy_cost=None,
-                  proxy_census_window=None) -> dict:
+                  proxy_census_window=None, eval_uncertainty: bool = False) -> dict:
     """The tool's options checked and gathered (raises ValueError), before a model or a device is touched. The proxy
     options are part of the result only with a positive ``proxy_weight``, ``proxy_cost`` and ``proxy_census_window``
-    ("HxW") only when the cost is "census" (without them it is "bt")."""
+    ("HxW") only when the cost is "census" (without them it is "bt"), ``eval_uncertainty`` only when it is set."""
     dirs = left_dir is not None or right_dir is not None
     if (dataset_root is not None) == dirs or (dirs and (left_dir is None or right_dir is None)):
         raise ValueError("give either --dataset-root or both --left-dir and --right-dir")
     if output_dir is None:
         raise ValueError("--output-dir is required.")
+    if eval_uncertainty and dataset_root is None:
+        raise ValueError("--eval-uncertainty needs --dataset-root (the ground truth it evaluates against).")
     if precision not in ("fp32", "bf16"):
         raise ValueError(f"--precision {precision}: adaptation trains, in fp32 or bf16 (fp8 is the inference-only forward).")
     if int(epochs) < 1:
@@ -157,7 +167,8 @@ def adapt_options(left_dir=None, right_dir=None, dataset_root=None, output_dir=N
                 height=height, width=width, epochs=int(epochs), batch_size=int(batch_size), lr=float(lr),
                 weight_decay=float(weight_decay), precision=precision, w_smooth=w_smooth, edge_gamma=edge_gamma,
                 occ_tol=occ_tol, uncertainty=bool(uncertainty), max_samples=int(max_samples), seed=int(seed),
-                base_channels=int(base_channels), read_threads=int(read_threads), ssim_weight=ssim_weight, **proxy)
+                base_channels=int(base_channels), read_threads=int(read_threads), ssim_weight=ssim_weight, **proxy,
+                **({"eval_uncertainty": True} if eval_uncertainty else {}))
 
 
 def _proxy_options(weight, only, num_disparities, block_size, mode, batch_size, width, cost=None,
@@ -269,17 +280,27 @@ class _InputLoader:
                 yield {"input": self.input[:n]}
 
 
-def _measure_epe(model, frames: _Frames, batches, H: int, W: int) -> dict:
+UNCERT_STEPS = 20  # cuts of the sparsification curves of --eval-uncertainty
+
+
+def _measure_epe(model, frames: _Frames, batches, H: int, W: int, eval_uncertainty: bool = False) -> tuple:
     """EPE and the other figures of ``predict.metrics_from_row`` over every sample, in eval mode (``Predictor.run`` with
-    the ground truth and no images: ``sd_disp_export``'s metric rows)."""
+    the ground truth and no images: ``sd_disp_export``'s metric rows), and with ``eval_uncertainty`` the figures of
+    ``uncert.aggregate_rows`` from the same forward (``sd_uncert_eval``), else None."""
     from .predict import Predictor, aggregate_rows
+    from .uncert import UncertaintyEval, aggregate_rows as aggregate_uncert_rows
 
     pred = Predictor(model, (W, H))  # puts the model into eval mode
-    rows = []
+    uncert = UncertaintyEval(UNCERT_STEPS, pred.device) if eval_uncertainty else None
+    rows, urows = [], []
     for hw, items in batches:
         for part in frames.load(hw, items):
-            rows.append(pred.run(part[0], part[1], part[2], images=False)["rows"].cpu().numpy().copy())
-    return aggregate_rows(np.concatenate(rows))
+            res = pred.run(part[0], part[1], part[2], images=False, **({"uncert": uncert} if uncert else {}))
+            rows.append(res["rows"].cpu().numpy().copy())
+            if uncert is not None:
+                urows.append(res["urows"].cpu().numpy().copy())
+    return (aggregate_rows(np.concatenate(rows)),
+            aggregate_uncert_rows(np.concatenate(urows), UNCERT_STEPS) if uncert is not None else None)
 
 
 def _train_config(ck: dict, opts: dict):
@@ -347,7 +368,8 @@ def adapt(checkpoint, *, model=None, device="cuda", **options) -> dict:
     dev = next(model.parameters()).device
     batches = plan_batches(items, opts["batch_size"])
     frames = _Frames(dev, opts["batch_size"], has_gt, opts["read_threads"])
-    before = _measure_epe(model, frames, batches, H, W) if has_gt else None
+    eval_unc = bool(opts.get("eval_uncertainty"))
+    before, unc_before = _measure_epe(model, frames, batches, H, W, eval_unc) if has_gt else (None, None)
     optimizer = FusedAdamW(model.parameters(), lr=opts["lr"], weight_decay=opts["weight_decay"])
     use_proxy = opts.get("proxy_weight", 0.0) > 0
     proxy = None
@@ -371,7 +393,7 @@ def adapt(checkpoint, *, model=None, device="cuda", **options) -> dict:
         order = [int(i) for i in rng.permutation(len(batches))]
         means = adapt_epoch(model, _InputLoader(frames, batches, H, W, order), dev, optimizer, loss, proxy=proxy)
         epochs.append({k: means[k] for k in keys})
-    after = _measure_epe(model, frames, batches, H, W) if has_gt else None
+    after, unc_after = _measure_epe(model, frames, batches, H, W, eval_unc) if has_gt else (None, None)
     model.train(False)
     save_checkpoint(out_dir / "adapted.pt", int(ck.get("epoch", 0)), model, optimizer, _train_config(ck, opts),
                     {f"adapt_{k}": v for k, v in epochs[-1].items() if v is not None},
@@ -385,6 +407,7 @@ def adapt(checkpoint, *, model=None, device="cuda", **options) -> dict:
                if opts["ssim_weight"] > 0 and loss is not None else {}),
             **({"proxy_mae_first": epochs[0]["proxy_mae"], "proxy_mae_last": epochs[-1]["proxy_mae"]} if use_proxy else {}),
             "epe_before": before["epe"] if before else None, "epe_after": after["epe"] if after else None,
+            **({"uncertainty_before": unc_before, "uncertainty_after": unc_after} if eval_unc else {}),
             "output": str(out_dir / "adapted.pt"), "elapsed_seconds": time.time() - started_at,
             "created_at_unix": time.time()}
     (out_dir / "adapt_meta.json").write_text(json.dumps(meta, indent=2), encoding="utf-8")
@@ -402,7 +425,7 @@ def main(argv=None) -> dict:
                              a.ssim_weight, proxy_weight=a.proxy_weight, proxy_only=a.proxy_only,
                              proxy_num_disparities=a.proxy_num_disparities, proxy_block_size=a.proxy_block_size,
                              proxy_mode=a.proxy_mode, proxy_cost=a.proxy_cost,
-                             proxy_census_window=a.proxy_census_window)
+                             proxy_census_window=a.proxy_census_window, eval_uncertainty=a.eval_uncertainty)
     except ValueError as e:
         parser.error(str(e))
     _resolve_device(a.device)

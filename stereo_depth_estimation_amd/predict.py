@@ -6,7 +6,8 @@
         [--write-sigma] [--png-level 1] [--read-threads 16] [--device cuda] \\
         [--write-ply (--calibration FILE.npz | --focal-px F --baseline-m B [--cx X --cy Y]) \\
          [--ply-stride 1] [--ply-min-depth M] [--ply-max-depth M]] \\
-        [--self-check [--check-occ-tol 0.5] [--check-photo-thr T] [--write-check] [--ply-visible-only]]
+        [--self-check [--check-occ-tol 0.5] [--check-photo-thr T] [--write-check] [--ply-visible-only]] \\
+        [--eval-uncertainty [--sparsification-steps 20]]
 
 Runs a trained checkpoint (``cli.save_checkpoint``'s format, or the reference's) over frames on disk and
 
@@ -39,6 +40,13 @@ taken as rectified: FoundationStereo's are, for a pair of directories that is th
 writes ``<name>.check.png``, the picture of the check; ``--ply-visible-only`` builds the cloud from the visible pixels
 alone (``disp_vis``), which removes the occluded and out-of-view "flying" points. Without ``--self-check`` every output
 is byte for byte what it is without these flags.
+
+``--eval-uncertainty`` (needs ``--dataset-root``) evaluates the log-variance head as well (``sd_uncert_eval`` on the same
+two maps and the native ground truth; uncert.py, INTEGRATION.md "Uncertainty evaluation"): each ``metrics.jsonl`` record
+gains an ``uncertainty`` object (the NLL in the training log's form, coverage at 0.5 / 1 / 2 / 3 times the predicted scale
+beside the nominal Laplace shares, AUSE, AURG, the two normalised sparsification curves of ``--sparsification-steps``
+cuts, and the saturated pixels), and ``predict_meta.json`` gains ``uncertainty`` (``uncert.aggregate_rows``) and
+``"eval_uncertainty": true``. Without the flag every file and the meta keep their bytes and keys, and no launch is added.
 
 ``--precision fp8``: the first batch is the calibration forward (its activations set the static e4m3 scales of all
 later batches), and the scales are per tensor over the batch, as in ``LiveDepthBatch``; there are no per-sample scales.
@@ -161,6 +169,23 @@ def cloud_options(write_ply: bool = False, output_root=None, calibration=None, f
                         cy=None if cy is None else float(cy), stride=int(ply_stride), z_range=z_range)
 
 
+def uncert_options(eval_uncertainty: bool = False, sparsification_steps=None, has_gt: bool = True) -> int | None:
+    """The ``--eval-uncertainty`` flags checked: the number of cuts, or None without the flag (the steps then must be
+    unset)."""
+    from .uncert import check_steps
+
+    if not eval_uncertainty:
+        if sparsification_steps is not None:
+            raise ValueError("--sparsification-steps: only with --eval-uncertainty.")
+        return None
+    if not has_gt:
+        raise ValueError("--eval-uncertainty needs --dataset-root (the ground truth it evaluates against).")
+    try:
+        return check_steps(20 if sparsification_steps is None else sparsification_steps)
+    except ValueError as e:
+        raise ValueError(f"--sparsification-steps: {e}") from None
+
+
 def ply_relpath(relpath: Path) -> Path:
     return relpath.with_suffix(".ply")
 
@@ -212,6 +237,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Residual (codes summed over the channels, 0..765) above which a visible pixel is a mismatch.")
     p.add_argument("--write-check", action="store_true", help="Also write <name>.check.png (needs --output-root).")
     p.add_argument("--ply-visible-only", action="store_true", help="Clouds from the visible pixels only (needs --write-ply).")
+    p.add_argument("--eval-uncertainty", action="store_true",
+                   help="Also evaluate the log-variance head: sparsification, AUSE, coverage, NLL (needs --dataset-root).")
+    p.add_argument("--sparsification-steps", type=int, default=None,
+                   help="Cuts of the sparsification curves, 1..256 (default 20; needs --eval-uncertainty).")
     return p
 
 
@@ -352,7 +381,7 @@ class Predictor:
 
     def run(self, left_u8: torch.Tensor, right_u8: torch.Tensor, gt_rgb: torch.Tensor | None = None,
             sigma: bool = False, images: bool = True, cloud: CloudOptions | None = None,
-            check: CheckOptions | None = None) -> dict:
+            check: CheckOptions | None = None, uncert=None) -> dict:
         """left_u8, right_u8 (and gt_rgb, the RGB24 ground truth): contiguous uint8 [n,Hs,Ws,3] on the model's device.
         Queues the batch on the current stream and returns device tensors without synchronising: ``disp_rgb`` and
         ``sigma_rgb`` uint8 [n,Hs,Ws,3] (None unless asked for), ``rows`` float64 [n,8] (None without gt_rgb). They are
@@ -362,7 +391,8 @@ class Predictor:
         lattice size. With ``check`` it holds ``disp_up`` and ``check_rows`` float64 [n,8], ``check_rgb`` uint8
         [n,Hs,Ws,3] with ``check.write_check`` and ``disp_vis`` float32 [n,Hs,Ws] with ``check.ply_visible_only``:
         sd_stereo_check on disp_up and the two source frames, ahead of the cloud stage, which then builds from
-        ``disp_vis`` in place of ``disp_up``."""
+        ``disp_vis`` in place of ``disp_up``. With ``uncert`` (an ``uncert.UncertaintyEval``; needs gt_rgb) it holds
+        ``urows`` float64 [n, 16 + 2 steps]: sd_uncert_eval on the same disp and logvar."""
         n, Hs, Ws = (int(v) for v in left_u8.shape[:3])
         for name, t in (("left_u8", left_u8), ("right_u8", right_u8), ("gt_rgb", gt_rgb)):
             if t is None:
@@ -373,6 +403,8 @@ class Predictor:
                                  f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
         if not (images or gt_rgb is not None or cloud is not None or check is not None):
             raise ValueError("Predictor.run: neither images nor metrics requested")
+        if uncert is not None and gt_rgb is None:
+            raise ValueError("Predictor.run: the uncertainty evaluation needs gt_rgb")
         sigma = bool(sigma and images)
         b = self._buffers(n, Hs, Ws, sigma)
         cb = self._cloud_buffers(n, Hs, Ws, cloud) if cloud is not None else None
@@ -397,6 +429,7 @@ class Predictor:
                    b["disp_rgb"].data_ptr() if images else None, b["sigma_rgb"].data_ptr() if sigma else None,
                    disp_up.data_ptr() if disp_up is not None else None,
                    b["rows"].data_ptr() if gt_rgb is not None else None, b["work"].data_ptr(), s)
+            urows = uncert.run(disp, logvar, gt_rgb, (Hs, Ws)) if uncert is not None else None
             if kb is not None:
                 L.call("sd_stereo_check", n, disp_up.data_ptr(), left_u8.data_ptr(), right_u8.data_ptr(), Hs, Ws,
                        check.occ_tol, check.photo_thr, None, None, L.ptr(kb["disp_vis"]), L.ptr(kb["vis_rgb"]),
@@ -417,6 +450,8 @@ class Predictor:
             res.update(disp_up=disp_up[:n], check_rows=kb["rows"][:n],
                        check_rgb=kb["vis_rgb"][:n] if kb["vis_rgb"] is not None else None,
                        disp_vis=kb["disp_vis"][:n] if kb["disp_vis"] is not None else None)
+        if uncert is not None:
+            res["urows"] = urows
         return res
 
 
@@ -429,10 +464,13 @@ class PredictPipeline:
 
     def __init__(self, predictor: Predictor, batch_size: int, has_gt: bool, images: bool, sigma: bool,
                  png_level: int = 1, read_threads: int = 16, cloud: CloudOptions | None = None,
-                 check: CheckOptions | None = None):
+                 check: CheckOptions | None = None, uncert=None):
         self.p, self.bmax, self.has_gt, self.images, self.sigma = predictor, batch_size, has_gt, images, sigma and images
         self.cloud = cloud
         self.check = check
+        self.uncert = uncert  # an uncert.UncertaintyEval or None
+        self._unc = [{}, {}]  # per slot: source size -> uncertainty rows [bmax, 16 + 2 steps] pinned
+        self.uncert_rows: list = []  # with uncert: the rows of every written batch, in order
         self._chk = [{}, {}]  # per slot: source size -> (check rows [bmax,8], picture [bmax,Hs,Ws,3] or None) pinned
         self.check_rows: list = []  # with check: the rows (float64 [n,8]) of every written batch, in order
         self._ply = [{}, {}]  # per slot: source size -> (records [bmax,cap,16], counts [bmax]) pinned
@@ -476,6 +514,13 @@ class PredictPipeline:
                                    if self.check.write_check else None)
         return self._chk[slot][hw]
 
+    def _pinned_uncert(self, slot: int, hw):
+        if hw not in self._unc[slot]:
+            from .uncert import row_len
+
+            self._unc[slot][hw] = torch.zeros(self.bmax, row_len(self.uncert.steps), dtype=torch.float64).pin_memory()
+        return self._unc[slot][hw]
+
     def decode(self, slot: int, hw, items) -> list[tuple]:
         """Source frames of one batch as parts (left, right[, ground truth]), each uint8 [n,Hs,Ws,3] pinned and of one
         source size, in the batch's order."""
@@ -501,8 +546,8 @@ class PredictPipeline:
 
     def device_work(self, slot: int, parts):
         """Queues one batch on the side stream. Returns (event, [(n, (Hs, Ws), pinned disp_rgb, sigma_rgb, rows,
-        records, counts, check rows, check picture)]); records and counts are None without a cloud, the last two
-        without a check (the picture also without ``write_check``)."""
+        records, counts, check rows, check picture, uncertainty rows)]); records and counts are None without a cloud,
+        the check's two without a check (the picture also without ``write_check``), the last without ``uncert``."""
         dev, outs = self.device, []
         with torch.cuda.stream(self.stream):
             off: dict = {}
@@ -516,7 +561,7 @@ class PredictPipeline:
                 for d, h in zip(up, part):
                     d.copy_(h, non_blocking=True)
                 res = self.p.run(up[0], up[1], up[2] if self.has_gt else None, sigma=self.sigma, images=self.images,
-                                 cloud=self.cloud, check=self.check)
+                                 cloud=self.cloud, check=self.check, **({"uncert": self.uncert} if self.uncert else {}))
                 o = off.get(hw, 0)  # parts of one size within a batch share the slot's buffers
                 off[hw] = o + n
                 h_disp, h_sigma, h_rows = self._pinned_out(slot, hw)
@@ -539,8 +584,13 @@ class PredictPipeline:
                     h_crow.copy_(res["check_rows"], non_blocking=True)
                     if h_cvis is not None:
                         h_cvis.copy_(res["check_rgb"], non_blocking=True)
+                h_urow = None
+                if self.uncert is not None:  # the rows ride the same copy-back
+                    h_urow = self._pinned_uncert(slot, hw)[o:o + n]
+                    h_urow.copy_(res["urows"], non_blocking=True)
                 outs.append((n, hw, h_disp[o:o + n] if self.images else None,
-                             h_sigma[o:o + n] if self.sigma else None, h_rows[o:o + n], h_pts, h_cnt, h_crow, h_cvis))
+                             h_sigma[o:o + n] if self.sigma else None, h_rows[o:o + n], h_pts, h_cnt, h_crow, h_cvis,
+                             h_urow))
             ev = torch.cuda.Event()
             ev.record(self.stream)
         return ev, outs
@@ -548,12 +598,14 @@ class PredictPipeline:
     def write(self, paths, sigma_paths, ev: torch.cuda.Event, outs, ply_paths=None, check_paths=None) -> np.ndarray:
         """Waits for the batch, writes its files (paths: one per sample in batch order, or None) and returns its rows.
         With a cloud, the batch's point counts are appended to ``point_counts``; with a check, its rows to
-        ``check_rows``."""
+        ``check_rows``; with ``uncert``, its rows to ``uncert_rows``."""
         from .cloud import write_ply_batch
 
         ev.synchronize()
         k, rows = 0, []
-        for n, hw, h_disp, h_sigma, h_rows, h_pts, h_cnt, h_crow, h_cvis in outs:
+        for n, hw, h_disp, h_sigma, h_rows, h_pts, h_cnt, h_crow, h_cvis, h_urow in outs:
+            if h_urow is not None:
+                self.uncert_rows.append(h_urow.numpy().copy())
             if h_crow is not None:
                 self.check_rows.append(h_crow.numpy().copy())
                 if check_paths is not None and h_cvis is not None:
@@ -584,8 +636,9 @@ def load_model(checkpoint, precision: str = "fp32", base_channels: int = 32, dev
 
 def _run(items: list[PredictItem], mode: str, source: str, described: dict, checkpoint, model, output_root, height,
          width, precision, base_channels, batch_size, max_samples, write_sigma, png_level, read_threads, device,
-         ply: dict | None = None) -> dict:
+         ply: dict | None = None, eval_uncertainty: bool = False, sparsification_steps=None) -> dict:
     ply, chk = _split_check(ply or {})
+    steps = uncert_options(eval_uncertainty, sparsification_steps, mode == "dataset")
     dev = _resolve_device(device)
     if batch_size < 1:
         raise ValueError(f"--batch-size must be >= 1, got: {batch_size}")
@@ -624,8 +677,13 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
 
     batches = plan_batches(items, batch_size)
     predictor = Predictor(model, (width, height))
+    uncert = None
+    if steps is not None:
+        from .uncert import UncertaintyEval
+
+        uncert = UncertaintyEval(steps, predictor.device)
     pipe = PredictPipeline(predictor, batch_size, has_gt, out_root is not None, write_sigma, png_level, read_threads,
-                           cloud, check)
+                           cloud, check, uncert)
     events, writes, held = [None, None], [None, None], [None, None]
     done: list = []  # (batch's items, future of its rows) in order
     try:
@@ -686,6 +744,13 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
     if has_gt:
         all_rows = np.concatenate([r for _, r in rows])
         meta.update(aggregate_rows(all_rows))
+    urows = None
+    if uncert is not None:
+        from .uncert import aggregate_rows as aggregate_uncert_rows
+        from .uncert import summary_from_row as uncert_summary_from_row
+
+        urows = np.concatenate(pipe.uncert_rows)
+        meta.update(eval_uncertainty=True, sparsification_steps=steps, uncertainty=aggregate_uncert_rows(urows, steps))
     if (has_gt or check is not None) and out_root is not None:  # without ground truth: the check's keys alone
         with open(out_root / "metrics.jsonl", "w", encoding="utf-8") as f:
             k = 0
@@ -696,6 +761,8 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
                         rec["points"] = int(points[k])
                     if crows is not None:
                         rec.update(check_summary_from_row(crows[k]))
+                    if urows is not None:
+                        rec["uncertainty"] = uncert_summary_from_row(urows[k], steps)
                     f.write(json.dumps(rec) + "\n")
                     k += 1
     if out_root is not None:
@@ -706,7 +773,8 @@ def _run(items: list[PredictItem], mode: str, source: str, described: dict, chec
 
 def predict_dataset(checkpoint, dataset_root, output_root=None, *, model=None, height=None, width=None,
                     precision: str = "fp32", base_channels: int = 32, batch_size: int = 32, max_samples: int = 0,
-                    write_sigma: bool = False, png_level: int = 1, read_threads: int = 16, device="cuda", **ply) -> dict:
+                    write_sigma: bool = False, png_level: int = 1, read_threads: int = 16, device="cuda",
+                    eval_uncertainty: bool = False, sparsification_steps=None, **ply) -> dict:
     """A FoundationStereo tree: disparity files under output_root (if given) and the metrics against the tree's ground
     truth. ``model``: a StereoUNet to use instead of loading ``checkpoint`` (height and width are then required).
     Returns the dict that is also written to ``predict_meta.json`` and printed as one JSON line. ``ply``: the keywords
@@ -714,13 +782,15 @@ def predict_dataset(checkpoint, dataset_root, output_root=None, *, model=None, h
     ply_stride=, ply_min_depth=, ply_max_depth=): also ``<scene>/<frame>.ply``, the coloured point cloud of each sample
     at the frame's own resolution. It also takes the keywords of ``check.check_options`` (self_check=True, then
     optionally check_occ_tol=, check_photo_thr=, write_check=, ply_visible_only=): the label-free check of every sample,
-    its totals under ``check`` in the returned dict and its per-sample keys in ``metrics.jsonl``."""
+    its totals under ``check`` in the returned dict and its per-sample keys in ``metrics.jsonl``.
+    ``eval_uncertainty=True`` (``sparsification_steps``: 20 when None) also evaluates the log-variance head: an
+    ``uncertainty`` object per ``metrics.jsonl`` record and in the returned dict."""
     _resolve_device(device)
     root = Path(dataset_root).expanduser().resolve()
     items = dataset_items(root)
     return _run(items, "dataset", str(root), {"dataset_root": str(root)}, checkpoint, model, output_root,
                 height, width, precision, base_channels, batch_size, max_samples, write_sigma, png_level, read_threads,
-                device, ply)
+                device, ply, eval_uncertainty, sparsification_steps)
 
 
 def predict_pairs(checkpoint, left_dir, right_dir, output_root, *, model=None, height=None, width=None,
@@ -728,8 +798,10 @@ def predict_pairs(checkpoint, left_dir, right_dir, output_root, *, model=None, h
                   write_sigma: bool = False, png_level: int = 1, read_threads: int = 16, device="cuda", **ply) -> dict:
     """Two directories of frames paired by stem: ``<output_root>/<stem>.png`` (and ``<stem>.ply`` with the ``ply``
     keywords of ``predict_dataset``), no metrics against ground truth. With ``self_check=True`` (and the other keywords
-    of ``check.check_options``) ``metrics.jsonl`` is written with the check's per-sample keys alone."""
+    of ``check.check_options``) ``metrics.jsonl`` is written with the check's per-sample keys alone. ``eval_uncertainty``
+    is refused: there is no ground truth here."""
     _resolve_device(device)
+    uncert_options(ply.pop("eval_uncertainty", False), ply.pop("sparsification_steps", None), has_gt=False)
     if output_root is None:
         raise ValueError("Nothing to do: no ground truth to evaluate against and no --output-root to write to.")
     left, right = Path(left_dir).expanduser().resolve(), Path(right_dir).expanduser().resolve()
@@ -758,6 +830,9 @@ def main(argv=None) -> dict:
             or a.check_photo_thr is not None:
         common.update(self_check=a.self_check, check_occ_tol=a.check_occ_tol, check_photo_thr=a.check_photo_thr,
                       write_check=a.write_check, ply_visible_only=a.ply_visible_only)
+    steps = uncert_options(a.eval_uncertainty, a.sparsification_steps, a.dataset_root is not None)  # raises early
+    if steps is not None:
+        common.update(eval_uncertainty=True, sparsification_steps=steps)
     if a.dataset_root is not None:
         return predict_dataset(a.checkpoint, a.dataset_root, a.output_root, **common)
     return predict_pairs(a.checkpoint, a.left_dir, a.right_dir, a.output_root, **common)
